@@ -16,6 +16,13 @@ Multi-GPU: one process per GPU (torchrun), each rank traces its own beam
 (rotated toroidally by 2*pi*rank/world; the plasma is axisymmetric), no
 data-path collective; one all_reduce of (n_psi+1) fp64 = make_beam's reduce
 (src/solve.jl:233-240).  scaling = "weak".
+
+A plain run sets up, warms up, times --steps steps and prints the line (value,
+ms_per_step, the roofline from the counted launch and the committed profiles).
+--dump-outputs DIR also writes the last timed step's outputs as .npy files.
+Everything measured beside the headline (library-path and host-pointer rates,
+ray-entry timing, the exact leg, the CPU-oracle baseline and the parity sample)
+runs only with --full.
 """
 from __future__ import annotations
 
@@ -87,19 +94,36 @@ def parse():
                     help="C4 (strong scaling): split ONE fan across the ranks (contiguous ray "
                          "ranges) instead of one rotated fan per rank; e.g. --n-rings 291 --shard "
                          "for the ~1e6-ray beam over 8 GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs beside the headline: the "
+                         "library-path and host-pointer rates, ray-entry timing, the exact "
+                         "(TORJ_TINY_ALPHA=0) leg, the CPU-oracle baseline and the parity sample "
+                         "against it (N > 1: the parity sample and the empty-shard fan-out "
+                         "timing); the --no-* switches below trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (state, "
+                         "status, steps, dP_shell, P_dep, traj) as DIR/<name>.npy, float64, at "
+                         "most 60 MB in all (a fixed seeded ray sample, DIR/ray_index.npy, when "
+                         "the beam is larger); N > 1: rank / device 0's shard")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU-oracle baseline and its parity sample")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the host-pointer (PCIe-inclusive) calls and the library-path rate "
-                         "(profiling passes)")
+                    help="--full: skip the host-pointer (PCIe-inclusive) calls and the library-path "
+                         "rate")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="target CPU time of the bounded cpu_baseline sample")
     ap.add_argument("--no-exact", action="store_true",
-                    help="skip the exact leg (the same timed loop with TORJ_TINY_ALPHA=0)")
+                    help="--full: skip the exact leg (the same timed loop with TORJ_TINY_ALPHA=0)")
     ap.add_argument("--no-beam-host", action="store_true",
-                    help="skip the C4-scale torj_trace_beam host-pointer call (N = 1)")
+                    help="--full: skip the C4-scale torj_trace_beam host-pointer call (N = 1)")
     ap.add_argument("--parity-rays", type=int, default=128,
-                    help="N > 1: rays of the oracle parity sample on rank 0 / device 0's shard")
-    return ap.parse_args()
+                    help="--full, N > 1: rays of the oracle parity sample on rank 0 / device 0's shard")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error(f"--steps {args.steps} < 1: the timed region needs at least one step")
+    if args.warmup < 0:
+        ap.error(f"--warmup {args.warmup} < 0")
+    return args
 
 
 def main():
@@ -250,6 +274,12 @@ def main():
     T._lib.check(L.torj_timing_read(plasma.handle, ctypes.byref(n_calls), ctypes.byref(t_trace),
                                     ctypes.byref(t_post)))
     T._lib.check(L.torj_timing(plasma.handle, 0))
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's outputs, before any later leg reuses the buffers
+        # (N > 1: this rank's shard and the reduced deposition vector)
+        dump_outputs(args.dump_outputs, d_state, d_status, d_steps, d_dP, d_Pdep,
+                     d_traj if n_save else None)
+        progress(f"outputs written to {args.dump_outputs}")
     kern_ms = t_trace.value / max(n_calls.value, 1)  # the trace kernel alone
     post_ms = t_post.value / max(n_calls.value, 1)   # deposition kernels (reference mode)
     tot_steps = torch.tensor([ray_steps_local], dtype=torch.float64, device=dev)
@@ -431,7 +461,7 @@ def main():
             out["multi_gpu"] = multi_gpu_block(per_rank, path="torchrun: one process per GPU, "
                                                "torj_trace_device_ex per rank + torch.distributed "
                                                "all_reduce of dP_shell")
-        if world == 1 and not args.no_host_api:
+        if args.full and world == 1 and not args.no_host_api:
             # the same beam through make_beam's library path (torj_trace_beam_device,
             # what `--gpus N` in one process times), so an N = 1 point of either path
             # compares with the N >= 2 lines of both
@@ -440,7 +470,7 @@ def main():
                                                     d_Pdep, d_traj if n_save else None,
                                                     ray_steps_local, value)
             progress("library-path steps done")
-        if world == 1 and not args.no_host_api:
+        if args.full and world == 1 and not args.no_host_api:
             out["host_api"] = host_api_rate(T, plasma, cfg, xp, Np, w, grid, n_save, ray_steps_local,
                                             pos, s0)
             progress("host-pointer call done")
@@ -449,19 +479,19 @@ def main():
                 progress("C4-scale torj_trace_beam call done")
             out["ray_entry"] = entry_timing(T, plasma, pos, dirs, omega, args.mode, t_entry)
         exact_out = None
-        if (world == 1 and args.absorption == "albajar" and not adaptive and not args.no_exact
-                and tiny_alpha() > 0.0):
+        if (args.full and world == 1 and args.absorption == "albajar" and not adaptive
+                and not args.no_exact and tiny_alpha() > 0.0):
             out["exact"], exact_out = exact_leg(T, L, plasma, launch, dev, args, value, kern_ms, post_ms,
                                                 d_state, d_status, d_steps, gpu_out)
             progress("exact (TORJ_TINY_ALPHA=0) leg done")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], parity = cpu_baseline(eq, xp, Np, w, omega, args, grid, gpu_out,
                                                        exact_out)
             if parity is not None:
                 if exact_out is not None:
                     out["exact"]["parity"] = parity.pop("exact")
                 out["parity"] = parity
-        elif world > 1 and args.parity_rays > 0 and args.integrator == "rk4":
+        elif args.full and world > 1 and args.parity_rays > 0 and args.integrator == "rk4":
             # rank 0's shard against the oracle (bounded sample, untimed)
             out["parity"] = parity_sample(eq, xp, Np, w, omega, args, grid, gpu_out, args.parity_rays)
             out["parity"]["shard"] = "rank 0"
@@ -587,12 +617,19 @@ def main_library(args):
     dep_ms = [t_post[k] / max(calls[k], 1) for k in range(N)]
     kern_ms, post_ms = trace_ms[0], dep_ms[0]
     rccl_ms = t_red.value / max(args.steps, 1)
-    # the fan-out + reduce overhead alone: empty shards, the same deposition vectors
-    empty = [dict(n=0, psi_grid=sh["psi_grid"], dP_shell=sh["dP_shell"]) for sh in shards]
-    t1 = time.perf_counter()
-    for _ in range(20):
-        trace_beam_device(plasma, cfg, args.n_psi, empty)
-    reduce_ms = (time.perf_counter() - t1) / 20 * 1e3
+    if args.dump_outputs:  # device 0's shard of the last timed step, its dP_shell the reduced vector
+        sh0 = shards[0]
+        dump_outputs(args.dump_outputs, sh0["state"], sh0["status"], sh0["steps"], sh0["dP_shell"],
+                     sh0["P_dep"], sh0["traj"])
+        progress(f"outputs written to {args.dump_outputs}")
+    reduce_ms = None
+    if args.full:
+        # the fan-out + reduce overhead alone: empty shards, the same deposition vectors
+        empty = [dict(n=0, psi_grid=sh["psi_grid"], dP_shell=sh["dP_shell"]) for sh in shards]
+        t1 = time.perf_counter()
+        for _ in range(20):
+            trace_beam_device(plasma, cfg, args.n_psi, empty)
+        reduce_ms = (time.perf_counter() - t1) / 20 * 1e3
     ms_per_step = elapsed / args.steps * 1e3
     value = ray_steps / (ms_per_step / 1e3)
     flop0 = (F.algorithmic_flops(cnt[0], n_gl=24) if args.absorption in ("albajar", "none")
@@ -682,7 +719,7 @@ def main_library(args):
             path="one process: torj_trace_beam_device, a host thread + stream per device, the "
                  "library's RCCL all-reduce (ncclCommInitAll)"),
     }
-    if args.parity_rays > 0 and args.integrator == "rk4":
+    if args.full and args.parity_rays > 0 and args.integrator == "rk4":
         sh0 = shards[0]
         p0 = parts[0]
         xp0, Np0, _, _ = T.ray_entry(plasma, p0[0], p0[1], omega, args.mode, gpu=True)
@@ -739,6 +776,48 @@ def check_line(out):
             raise KeyError("multi_gpu: the reduce's participants (" + " or ".join(
                 ", ".join(ks) for ks in MULTI_GPU_COMM_KEYS.values()) + ")")
     return out
+
+
+# --dump-outputs: the byte budget of all arrays together, and the seed of the
+# ray sample taken when the beam's outputs exceed it
+DUMP_BYTES = 60_000_000
+DUMP_SEED = 20240517
+
+
+def dump_sample(n, bytes_per_ray, bytes_fixed):
+    """The rays --dump-outputs keeps: all n when they fit DUMP_BYTES, else a
+    sorted sample without replacement from a generator seeded with DUMP_SEED
+    (a function of n and the array shapes alone, so two builds keep the same rays)."""
+    k = int(min(n, max(1, (DUMP_BYTES - bytes_fixed) // bytes_per_ray)))
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirname, state, status, steps, dP_shell, P_dep, traj):
+    """Write one trace's outputs, laid out as torj_hip.trace returns them, to
+    dirname/<name>.npy in float64: state (rays, 7), status, steps and P_dep
+    (rays), traj (rays, saved points, 5; NaN past a ray's stop; absent without
+    a trajectory), dP_shell (n_psi + 1) and ray_index, the fan indices of the
+    rows (dump_sample).  The arguments are the device-layout buffers: state
+    (7, n), traj (saved points, 5, n), torch tensors or arrays."""
+    def host(a):
+        return np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+
+    n = int(status.shape[0])
+    per_ray = 8 * (7 + 4) + (8 * 5 * int(traj.shape[0]) if traj is not None else 0)
+    idx = dump_sample(n, per_ray, 8 * int(dP_shell.shape[0]))
+    arrays = {"ray_index": idx,
+              "state": host(state).T[idx],
+              "status": host(status)[idx],
+              "steps": host(steps)[idx],
+              "P_dep": host(P_dep)[idx],
+              "dP_shell": host(dP_shell)}
+    if traj is not None:
+        arrays["traj"] = host(traj)[:, :, idx].transpose(2, 0, 1)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def library_path_rate(T, plasma, cfg, args, n, d_x0, d_N0, d_w, d_grid, d_xl, d_s0, d_state, d_status,

@@ -30,7 +30,7 @@ if [ -n "$AB" ]; then
   done
 fi
 if [ -n "$FULL_BENCH" ]; then
-  timeout -k 10 600 python bench.py $FULL_ARGS > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
+  timeout -k 10 600 python bench.py --full $FULL_ARGS > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
   grep '^{' $O/bench.log > $O/bench.json
   python - <<'PY'
 import json, os

@@ -35,6 +35,77 @@ def test_gpus_below_one_rejected():
     assert r.returncode != 0 and "--gpus 0" in r.stderr
 
 
+def test_steps_below_one_rejected():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps 0" in r.stderr and r.stdout.strip() == ""
+
+
+def test_full_and_dump_outputs_are_options_off_by_default(monkeypatch):
+    B = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = B.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = B.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_layout_and_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 arrays laid out as torj_hip.trace returns
+    them; a beam whose outputs exceed the byte budget keeps a sorted ray sample
+    that depends on the shapes alone (the same rays from run to run)."""
+    import numpy as np
+
+    B = _bench_module()
+    n, n_save, n_psi = 37, 3, 10
+    rng = np.random.default_rng(0)
+    state, traj = rng.normal(size=(7, n)), rng.normal(size=(n_save, 5, n))
+    traj[2, :, 5] = np.nan
+    status, steps = rng.integers(0, 5, n).astype(np.int32), rng.integers(0, 300, n).astype(np.int32)
+    dP, Pdep = rng.normal(size=n_psi + 1), rng.normal(size=n)
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    B.dump_outputs(str(tmp_path / "all"), state, status, steps, dP, Pdep, traj)
+    a = load(tmp_path / "all")
+    assert sorted(a) == ["P_dep", "dP_shell", "ray_index", "state", "status", "steps", "traj"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert np.array_equal(a["ray_index"], np.arange(n))
+    assert np.array_equal(a["state"], state.T) and np.array_equal(a["status"], status)
+    assert np.array_equal(a["steps"], steps) and np.array_equal(a["P_dep"], Pdep)
+    assert np.array_equal(a["dP_shell"], dP)
+    assert a["traj"].shape == (n, n_save, 5)
+    assert np.array_equal(a["traj"], traj.transpose(2, 0, 1), equal_nan=True)
+
+    B.dump_outputs(str(tmp_path / "notraj"), state, status, steps, dP, Pdep, None)
+    assert "traj" not in load(tmp_path / "notraj")
+
+    # a budget that 37 rays exceed: (7 + 4 + 5 * 3) doubles per ray, 11 for dP_shell
+    per_ray = 8 * (7 + 4 + 5 * n_save)
+    monkeypatch.setattr(B, "DUMP_BYTES", 8 * (n_psi + 1) + 20 * per_ray + per_ray // 2)
+    B.dump_outputs(str(tmp_path / "s1"), state, status, steps, dP, Pdep, traj)
+    B.dump_outputs(str(tmp_path / "s2"), state, status, steps, dP, Pdep, traj)
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    idx = s1["ray_index"].astype(int)
+    assert len(idx) == 20 and len(set(idx)) == 20 and (np.diff(idx) > 0).all() and idx.max() < n
+    assert sum(v.nbytes for v in s1.values()) <= B.DUMP_BYTES
+    assert all(np.array_equal(s1[k], s2[k], equal_nan=True) for k in s1)
+    assert np.array_equal(s1["state"], state.T[idx]) and np.array_equal(s1["steps"], steps[idx])
+    assert np.array_equal(s1["traj"], traj.transpose(2, 0, 1)[idx], equal_nan=True)
+    assert np.array_equal(s1["dP_shell"], dP)  # not per ray: whole
+
+
+def test_default_dump_fits_64_mb():
+    """The headline beam (100 203 rays, 20 saved points): the sample's arrays
+    stay within 64 MB, and every ray is kept where the outputs fit."""
+    B = _bench_module()
+    per_ray, fixed = 8 * (7 + 4 + 5 * 20), 8 * 1001
+    idx = B.dump_sample(100203, per_ray, fixed)
+    assert 60000 < len(idx) < 100203 and len(idx) * per_ray + fixed <= B.DUMP_BYTES <= 64_000_000
+    assert len(B.dump_sample(100203, 8 * (7 + 4), fixed)) == 100203
+
+
 def _bench_module():
     import importlib.util
 

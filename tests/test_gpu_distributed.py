@@ -95,7 +95,7 @@ def test_bench_torchrun_two_ranks_same_device(gpu):
     env = dict(os.environ, TORJ_BENCH_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-rings", "20", "--parity-rays", "32"]
+           "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-rings", "20", "--parity-rays", "32"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
