@@ -137,7 +137,7 @@ def test_split_counters_match_fused(gpu, T, hplasma, zflag):
 
 @pytest.mark.parametrize("tiny", ["1e-20", "0"])
 def test_zero_flags_bit_identical(gpu, T, hplasma, tiny):
-    """The block zero flags (torj_hip.hip zero_box_flag: the trajectory kernel
+    """The block zero flags (torj_k_traj.hpp zero_box_flag: the trajectory kernel
     proves per ray and ring block that every stored stage point has alpha = +-0,
     and an alpha wave whose rays are all flagged writes 0 without evaluating)
     change no output bit: TORJ_ALPHA_ZFLAG=0 against the default on the split
@@ -322,7 +322,7 @@ def test_split_warm_deferred_points(gpu, T, hplasma, model):
 def test_split_serial_equals_overlapped(gpu, T, hplasma, deposition):
     """The trajectory and alpha kernels read the scan's stop word (sinfo) while
     the scan of an earlier block may still be writing it on another stream; the
-    read only skips work nobody reads (torj_hip.hip traj_body).  Held here: with
+    read only skips work nobody reads (torj_k_traj.hpp traj_body).  Held here: with
     rays ABSORBED mid-block (P_min raised), TORJ_SPLIT_SERIAL=1 (every kernel on
     one stream, no overlap) and the default overlap give bit-identical state,
     steps, status, deposition and trajectory."""
@@ -622,7 +622,7 @@ def test_nan_alpha_replay_bit_identical(gpu, T, hplasma, mode):
 def test_traj_tile_bit_identical_to_global_fallback(gpu, T, hplasma, tile, caps):
     """k_traj_tile (TORJ_TRAJ_LDS=2) stages per wave only the coefficient tile
     its rays can reach in the block and reads a stencil outside it from global
-    memory (torj_hip.hip traj_body); k_traj_cell (=3) does the same with the
+    memory (torj_k_traj.hpp traj_body); k_traj_cell (=3) does the same with the
     cells' power-form records (torj_math.hpp cell_sums).  Either kernel with the
     tile's margin at 0 (rays leave their tile mid-block: the per-evaluation
     fallback), with a small cap (some waves untiled) and with no tile at all

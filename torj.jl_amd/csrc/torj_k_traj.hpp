@@ -1,0 +1,463 @@
+// torj_k_traj.hpp -- the split pipeline's trajectory kernels: the zero box,
+// cold_step, traj_run / traj_body and k_traj, k_traj_lds, k_traj_tile,
+// k_traj_cell.  Needs torj_args.hpp and the math headers only -- never
+// torj_k_fused.hpp: torj_traj.hip compiles this file without the fused kernels
+// and their __constant__ tables.
+// (a slice of torj_hip.hip / torj_traj.hip: included after `using namespace torj`)
+#pragma once
+#include "torj_args.hpp"
+#include "torj_fitdepo.hpp"
+
+// ---------------------------------------------------------------------------
+// Split RK4 path: trajectory and optical depth as separate, overlapped kernels
+// (fixed-step RK4, Albajar).
+//
+// In sys! (src/solve.jl:112-114) dx/ds and dN/ds are gradΛ!(x, N) alone: the
+// absorption only drives u[7].  So the trajectory of every ray is fixed before
+// any alpha is known, and the 4 x n_steps alpha evaluations of a ray are
+// independent of each other -- the step's chain is the cheap cold RHS, the
+// expensive part is embarrassingly parallel.  Per block of B steps:
+//   k_traj      one lane per ray: the cold RK4 steps (the same arithmetic as
+//               ray_segment), writing each stage's alpha inputs (X, Y, |N|,
+//               N_par, Te), psi per step, chunk-boundary states, trajectory
+//               samples; stops LEFT_PLASMA / NAN exactly as ray_segment;
+//   k_alpha_pts one lane per (ray, step, stage): abs_albajar_fast at the
+//               stored inputs -- a fully occupied grid, no step chain;
+//   k_tau_scan  one lane per ray, in step order: tau += ds/6 (a0 + 2a1 + 2a2 +
+//               a3) with ray_segment's fma order, P = exp(-tau), the ABSORBED
+//               check at chunk boundaries (after T's psi check, as the
+//               reference), make_ray's dP/ds samples, binned deposition, tau in
+//               the trajectory samples;
+// then k_split_final assembles the final state (a ray the scan stops earlier
+// than the trajectory takes its chunk-boundary state, or replays the last
+// steps when alpha itself went non-finite).  k_traj of block b+1 runs on the
+// caller's stream while k_alpha_pts / k_tau_scan of block b run on a second
+// stream: the trajectory waves (~1.5 per SIMD on a 1e5-ray beam) and the alpha
+// waves share the SIMDs.  A wave of k_alpha_pts holds the 64 rays of a 64-ray
+// group at one (step, stage): the same lanes as the fused kernel's wave there,
+// so the per-wave Bessel-level ballot and every alpha are the same bits.
+// ---------------------------------------------------------------------------
+// The alpha-input box of one ray over a block (round 6): the range of ln Te,
+// Y, N_par^2 and N_perp^2 over every stage point the trajectory kernel stored.
+// zero_box_flag proves from it that abs_albajar_fast_body returns +-0 at every
+// one of them -- all Te < 20 eV, or each harmonic m = 2, 3 absent (m Y <
+// sqrt(1 - N_par^2)) or an exact zero (every node's exp(mu (1 - gamma))
+// underflows: gamma_min > 1 + 760 / mu, with gamma_min >= m Y / (1 + |N_par|)
+// on the resonance gamma - N_par u_par = m Y, |u_par| <= gamma) -- the early
+// settle of abs_albajar_fast_body (and its exact-zero test), which returns +0
+// there, decided for a whole block with relative margins of 1e-9 against
+// their roundings.  k_alpha_pts then writes 0 for a wave whose 64 rays all
+// carry the flag instead of evaluating it (42 % of its waves settle early on the
+// headline beam).
+struct ZBox {
+    double lte = -INFINITY, ylo = INFINITY, yhi = -INFINITY, np2 = -INFINITY, perp = INFINITY;
+    double chk = 0.0;  // stays 0 unless an input was NaN or infinite
+};
+// v_max_f64 / v_min_f64 as one instruction each: fmax / fmin would first
+// quiet both operands (two more v_max_f64 per call, 24 VALU per stage point
+// for the box instead of 12); NaN inputs are caught by chk, not by these
+__device__ __forceinline__ double zb_max(double a, double b) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double zb_min(double a, double b) {
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ void zero_box_add(ZBox &b, double lnTe, double Y, double Npar, double N2) {
+    const double np2 = Npar * Npar;
+    b.lte = zb_max(b.lte, lnTe);
+    b.ylo = zb_min(b.ylo, Y);
+    b.yhi = zb_max(b.yhi, Y);
+    b.np2 = zb_max(b.np2, np2);
+    b.perp = zb_min(b.perp, fma(-1e-9, N2, N2 - np2));  // N_perp^2 with a relative margin
+    b.chk = fma((lnTe + Y) + (Npar + N2), 0.0, b.chk);  // NaN once any input is NaN or infinite
+}
+__device__ __forceinline__ bool zero_box_flag(const ZBox &b) {
+    if (!(b.chk == 0.0)) return false;
+    if (b.lte < 2.9957322735539909 - 1e-9) return true;  // every Te < 20 eV (ln 20)
+    if (!(b.ylo > 1e-200 && b.yhi < 1e200 && b.perp > 0.0 && b.np2 < 1.0 - 1e-9 && b.lte < 700.0))
+        return false;
+    constexpr double kMuTe = kMe * kC * kC / kE;  // mu Te (albajar_pre)
+    const double delta = 760.0 * (1.0 + 1e-9) * exp(b.lte) * (1.0 / kMuTe);  // 760 / mu_min
+    const double npm = sqrt(b.np2), sq = sqrt(1.0 - b.np2);
+    bool ok = true;
+#pragma unroll
+    for (int m = 2; m <= 3; m++) {
+        const bool absent = m * b.yhi * (1.0 + 1e-9) < sq * (1.0 - 1e-9);
+        const bool zero = m * b.ylo > (1.0 + delta) * (1.0 + npm) * (1.0 + 1e-9);
+        ok = ok && (absent || zero);
+    }
+    return ok;
+}
+
+// One cold RK4 step of ray_segment's arithmetic (plasma_point with ln Te, as
+// the absorbing kernels evaluate it); STORE: this step's alpha inputs -> ain.
+// PSI: stage 0's stencil also sums psi at x (the step's start), returned in
+// *psi_x -- the psi the previous step's end needs (traj_run), bit for bit the
+// eval_one at that point.
+template <bool STORE, int NS = kNF, class CS = const double *, bool PSI = false>
+__device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
+                                          const SplitArgs &sp, int j, int i, const double x[3],
+                                          const double N[3], double xn[3], double Nn[3],
+                                          double *psi_x, ZBox &zb, bool zon) {
+    const double hds = 0.5 * a.ds, ds6 = a.ds / 6.0;
+    double acc[6] = {0, 0, 0, 0, 0, 0}, xt[3], Nt[3], k[6];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        xt[c] = x[c];
+        Nt[c] = N[c];
+    }
+#pragma unroll 1
+    for (int st = 0; st < 4; st++) {
+        PlasmaPoint p;
+        if constexpr (PSI) {
+            // stage 0 with the sixth field (a branch around whole evaluations: a
+            // per-field gate inside the stencil split its blocks and spilled)
+            if (st == 0) {
+                plasma_point<true, NS, CS, true>(coef, a.g, a.k, xt, p);
+                *psi_x = p.psi;
+            } else {
+                plasma_point<true, NS>(coef, a.g, a.k, xt, p);
+            }
+        } else {
+            plasma_point<true, NS>(coef, a.g, a.k, xt, p);
+        }
+        double Npar, inv;
+        dispersion_grad(p, Nt, a.mode, k, &Npar, &inv);
+        if constexpr (STORE) {
+            double *o = sp.ain + ((size_t)(j * 4 + st) * sp.nf) * a.n + i;
+            const double N2 = Nt[0] * Nt[0] + Nt[1] * Nt[1] + Nt[2] * Nt[2];
+            if (zon) zero_box_add(zb, p.lnTe, p.Y, Npar, N2);
+            o[0] = p.X;
+            o[(size_t)a.n] = p.Y;
+            o[3 * (size_t)a.n] = Npar;
+            if (sp.nf > kAinF) {  // the warm inputs as ray_rhs_m<2 / 3> forms them
+                o[2 * (size_t)a.n] = sqrt(N2);
+                o[4 * (size_t)a.n] = exp(p.lnTe);
+                o[kAinF * (size_t)a.n] = inv;
+            } else if constexpr (TORJ_AIN_TRAJ_MATH) {
+                // |N| and Te by the functions k_alpha_pts would apply (the same
+                // bits), on the trajectory chain, which has slack once the alpha
+                // chain is the pipeline's critical one
+                o[2 * (size_t)a.n] = sqrt_pos(N2);
+                o[4 * (size_t)a.n] = exp_fast<true>(p.lnTe);
+            } else {
+                // |N|^2 and ln Te: k_alpha_pts takes the square root and the
+                // exponential (the same functions ray_rhs applies), off the
+                // latency-bound trajectory chain and onto the parallel alpha lanes
+                o[2 * (size_t)a.n] = N2;
+                o[4 * (size_t)a.n] = p.lnTe;
+            }
+        }
+        const double wgt = (st == 0 || st == 3) ? 1.0 : 2.0;
+        const double h = (st < 2) ? hds : a.ds;
+#pragma unroll
+        for (int c = 0; c < 6; c++) acc[c] = fma(wgt, k[c], acc[c]);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            xt[c] = fma(h, k[c], x[c]);
+            Nt[c] = fma(h, k[3 + c], N[c]);
+        }
+    }
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        xn[c] = x[c] + ds6 * acc[c];
+        Nn[c] = N[c] + ds6 * acc[3 + c];
+        bad |= !isfinite(xn[c]) || !isfinite(Nn[c]);
+    }
+    return bad;
+}
+
+// Where the trajectory kernel reads the field coefficients:
+//   kTrajL2    the global array through L1 / L2 (any grid);
+//   kTrajLds   the whole grid staged in LDS (6 fp64 per node, 161 KB for a 56 x 56
+//              grid: one workgroup of up to 8 waves per CU);
+//   kTrajTile  per wave and block, only the tile of nodes its rays can reach in
+//              the block's kb steps (|dx/ds| = 1, so within (kb + 1) ds of where
+//              they start), a few KB: the kernel is no longer capped at one
+//              workgroup per CU, and its waves share every SIMD with the alpha
+//              waves.  A stencil outside the tile reads the global array (the
+//              same values: results bit-identical in every mode).
+//   kTrajCell  per wave and block, the tile of CELLS its rays can reach, each
+//              cell's bicubic in power form (torj_math.hpp cell_sums: 28 fma per
+//              field with its gradient against the node stencil's 44, no basis
+//              weights); the same fallback to the global cell table.
+enum { kTrajL2 = 0, kTrajLds = 1, kTrajTile = 2, kTrajCell = 3 };
+constexpr int kTrajLdsNS = 6;
+static_assert(kTrajLdsNS == kTileNS, "LDS layouts");
+
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+// the cell index axis_setup gives a coordinate (monotone in x)
+__device__ __forceinline__ int cell_index(double x, double x1, double xn, double invh, int n) {
+    const int i = (int)floor((clampd(x, x1, xn) - x1) * invh);
+    return i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
+}
+
+#ifndef TORJ_TRAJ_PREWAIT
+#define TORJ_TRAJ_PREWAIT 1
+#endif
+// the trajectory steps of one ray over the block, from its carry (x, N, steps)
+template <int DEPO, bool TRAJ, int NS, class CS>
+__device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp, CS coef, int i,
+                                         double x[3], double N[3], int steps, int st) {
+    if (sp.k0 == 0) {
+        if constexpr (DEPO != kDepoNone) {
+            const double psi0 = eval_one<NS>(coef, a.g, sqrt(x[0] * x[0] + x[1] * x[1]), x[2], F_PSI);
+            sp.spsi[i] = psi0;  // the scan's psi_a at step 0
+            if constexpr (DEPO == kDepoSamples) {
+                a.smp_psi[smp_at(0, i, a.smp_rows)] = psi0;
+                a.smp_dpds[smp_at(0, i, a.smp_rows)] = 0.0;
+            }
+        }
+    }
+    const int s_end = min(a.n_steps, sp.k0 + sp.kb);
+    // psi at the end of step s - 1 is psi at x_s, which step s's stage 0 sums
+    // from its own stencil (cold_step<PSI>): the end-of-step work that needs it
+    // (make_ray's psi sample, the binned deposition's psi, the psi_exit check)
+    // runs one iteration late, before step s's outcome is looked at, so the
+    // order of stops is ray_segment's (psi check, then the next step's NaN);
+    // the block's last step takes the one eval_one left.  A ray stopped by the
+    // check has stored step s's alpha inputs too -- beyond its steps, so
+    // k_alpha_pts and the scan never read them.
+    auto step_end = [&](int k, double psi_b) -> bool {  // after step k (steps = k + 1)
+        const int sk = k + 1;
+        if constexpr (DEPO == kDepoSamples) a.smp_psi[smp_at(sk, i, a.smp_rows)] = psi_b;
+        if constexpr (DEPO == kDepoBinned) sp.psib[(size_t)(k - sp.k0) * a.n + i] = psi_b;
+        return a.chunk_steps > 0 && (sk % a.chunk_steps) == 0 && psi_b > a.psi_exit;  // src/solve.jl:174
+    };
+    const int s_first = steps;
+    bool pending = false;  // step steps - 1 still needs its psi
+    // (a value and a flag, not a pointer: a local behind a conditional pointer
+    // lived in scratch, 56 B per lane, and slowed the kernel by ~14 %)
+    ZBox zb;
+    const bool zon = sp.zflag != nullptr;
+#if defined(__HIP_DEVICE_COMPILE__) && TORJ_TRAJ_PREWAIT
+    // every load before the step loop complete here (s_waitcnt vmcnt(0)): the
+    // compiler otherwise waits at the loop header for the carry's loads, every
+    // step, and on gfx9 vmcnt counts stores too -- each step would then wait for
+    // its own last stage's alpha-input stores to reach memory
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+    for (int s = s_first; s < s_end; s++) {
+        double xn[3], Nn[3], psi_x;
+        const bool bad = cold_step<true, NS, CS, true>(a, coef, sp, s - sp.k0, i, x, N, xn, Nn, &psi_x, zb, zon);
+        if (pending) {
+            pending = false;
+            if (step_end(s - 1, psi_x)) {
+                st = ST_LEFT_PLASMA;
+                break;
+            }
+        }
+        if (bad) {
+            st = ST_NAN;
+            break;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            x[c] = xn[c];
+            N[c] = Nn[c];
+        }
+        steps = s + 1;
+        const bool check = a.chunk_steps > 0 && (steps % a.chunk_steps) == 0;
+        pending = DEPO != kDepoNone || check;
+        if constexpr (TRAJ) {
+            if (a.traj_stride > 0 && (steps % a.traj_stride) == 0) {
+                double *T = a.traj + (size_t)(steps / a.traj_stride - 1) * 5 * a.n + i;
+                T[0] = x[0];
+                T[(size_t)a.n] = x[1];
+                T[2 * (size_t)a.n] = x[2];
+                T[4 * (size_t)a.n] = (a.s0 ? a.s0[i] : 0.0) + steps * a.ds;
+            }
+        }
+        if (check) {
+            double *cb = sp.cbx + (size_t)(steps / a.chunk_steps) * 6 * a.n + i;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                cb[c * (size_t)a.n] = x[c];
+                cb[(3 + c) * (size_t)a.n] = N[c];
+            }
+        }
+    }
+    double invR;
+    if (pending && step_end(steps - 1, eval_one<NS>(coef, a.g, cyl_radius(x, invR), x[2], F_PSI)))
+        st = ST_LEFT_PLASMA;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        sp.tx[c * (size_t)a.n + i] = x[c];
+        sp.tx[(3 + c) * (size_t)a.n + i] = N[c];
+    }
+    sp.tinfo[i] = make_info(steps, st);
+    if (zon) sp.zflag[i] = zero_box_flag(zb) ? 1 : 0;
+}
+
+
+template <int DEPO, bool TRAJ, int MODE>
+__device__ __forceinline__ void traj_body(const TraceArgs &a, const SplitArgs &sp) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double x[3] = {0, 0, 0}, N[3] = {0, 0, 0};
+    int steps = 0, st = ST_OK;
+    bool live = i < a.n;
+    if (live) {
+        if (sp.k0 == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                x[c] = a.x0[c * a.n + i];
+                N[c] = a.N0[c * a.n + i];
+                sp.cbx[c * (size_t)a.n + i] = x[c];
+                sp.cbx[(3 + c) * (size_t)a.n + i] = N[c];
+            }
+        } else {
+            const int v = sp.tinfo[i];
+            steps = info_steps(v);
+            st = info_status(v);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                x[c] = sp.tx[c * (size_t)a.n + i];
+                N[c] = sp.tx[(3 + c) * (size_t)a.n + i];
+            }
+        }
+        // a ray the scan has stopped (ABSORBED) needs no more trajectory.  sinfo is
+        // written by k_tau_scan on another stream while this kernel may run, so the
+        // read can be stale.  INVARIANT: this early-out only saves work, it never
+        // decides an output -- a stale OK just traces steps nobody reads (the scan
+        // stopped first; k_split_final rebuilds the state from the chunk-boundary
+        // copy and the scan's carry).  Keep it that way: tests/test_gpu_split.py
+        // test_split_serial_equals_overlapped holds both orders bit-identical.
+        live = st == ST_OK && !(sp.k0 > 0 && info_status(sp.sinfo[i]) != ST_OK);
+        // a ray without trajectory steps in this block needs no alpha in it
+        if (!live && sp.zflag) sp.zflag[i] = 1;
+    }
+    if constexpr (MODE == kTrajTile) {
+        // one wave per workgroup: the wave's live rays' (R, Z) box, widened by
+        // the path the block can take, and its nodes staged in LDS
+        __shared__ __attribute__((aligned(16))) double s_tile[kTileNodes * kTileNS];
+        const double R = sqrt(x[0] * x[0] + x[1] * x[1]);
+        const double inf = __builtin_inf();
+        const double rmin = wave_min(live ? R : inf), rmax = wave_max(live ? R : -inf);
+        const double zmin = wave_min(live ? x[2] : inf), zmax = wave_max(live ? x[2] : -inf);
+        if (!(rmin <= rmax && zmin <= zmax)) return;  // no live ray in the wave (wave-uniform)
+        const double m = (double)(sp.kb + 1) * a.ds * sp.tile_margin;
+        const int iR0 = cell_index(rmin - m, a.g.R1, a.g.Rn, a.g.invhR, a.g.nR),
+                  iR1 = cell_index(rmax + m, a.g.R1, a.g.Rn, a.g.invhR, a.g.nR),
+                  iZ0 = cell_index(zmin - m, a.g.Z1, a.g.Zn, a.g.invhZ, a.g.nZ),
+                  iZ1 = cell_index(zmax + m, a.g.Z1, a.g.Zn, a.g.invhZ, a.g.nZ);
+        TileCoef tc{a.coef, s_tile, iR0, iZ0, iR1 - iR0 + 4, iZ1 - iZ0 + 4};
+        if (tc.tw * tc.th > sp.tile_cap) {
+            tc.tw = tc.th = 0;  // too wide for the tile: every stencil from global memory
+        } else {
+            const int mR = a.g.nR + 2, cnt = tc.tw * tc.th * kTileNS;
+            for (int k = threadIdx.x; k < cnt; k += 64) {
+                const int node = k / kTileNS, f = k - node * kTileNS;
+                const int zr = node / tc.tw, rr = node - zr * tc.tw;
+                s_tile[k] = a.coef[((size_t)(iZ0 + zr) * mR + iR0 + rr) * kNF + f];
+            }
+        }
+        __syncthreads();
+        if (!live) return;
+        traj_run<DEPO, TRAJ, kTileNS>(a, sp, tc, i, x, N, steps, st);
+    } else if constexpr (MODE == kTrajCell) {
+        // the cells the wave's live rays can reach in the block (the node tile's
+        // box, by cell), their power-form records staged in LDS
+        __shared__ __attribute__((aligned(16))) double s_cell[kTileCells * kCellRec];
+        const double R = sqrt(x[0] * x[0] + x[1] * x[1]);
+        const double inf = __builtin_inf();
+        const double rmin = wave_min(live ? R : inf), rmax = wave_max(live ? R : -inf);
+        const double zmin = wave_min(live ? x[2] : inf), zmax = wave_max(live ? x[2] : -inf);
+        if (!(rmin <= rmax && zmin <= zmax)) return;  // no live ray in the wave (wave-uniform)
+        const double m = (double)(sp.kb + 1) * a.ds * sp.tile_margin;
+        const int iR0 = cell_index(rmin - m, a.g.R1, a.g.Rn, a.g.invhR, a.g.nR),
+                  iR1 = cell_index(rmax + m, a.g.R1, a.g.Rn, a.g.invhR, a.g.nR),
+                  iZ0 = cell_index(zmin - m, a.g.Z1, a.g.Zn, a.g.invhZ, a.g.nZ),
+                  iZ1 = cell_index(zmax + m, a.g.Z1, a.g.Zn, a.g.invhZ, a.g.nZ);
+        // the box is wave-uniform: scalar registers for the copy's loop
+        const int cR0 = __builtin_amdgcn_readfirstlane(iR0), cZ0 = __builtin_amdgcn_readfirstlane(iZ0);
+        const int cw = __builtin_amdgcn_readfirstlane(iR1 - iR0 + 1), ch = __builtin_amdgcn_readfirstlane(iZ1 - iZ0 + 1);
+        TileCell tc{a.cellp, s_cell, cR0, cZ0, cw, ch};
+        if (cw * ch > sp.tile_cap) {
+            tc.cw = tc.ch = 0;  // too wide for the tile: every cell from global memory
+        } else {
+            // one cell record (48 x 16 B) per pass, lanes 0..47 (measured: four
+            // loads in flight per lane over the flattened tile is no faster)
+            const int cR = a.g.nR - 1;
+            const Dbl2 *src = reinterpret_cast<const Dbl2 *>(a.cellp);
+            Dbl2 *dst = reinterpret_cast<Dbl2 *>(s_cell);
+            for (int zr = 0; zr < ch; zr++)
+                for (int rr = 0; rr < cw; rr++)
+                    if (threadIdx.x < kCellRec / 2)
+                        dst[(zr * cw + rr) * (kCellRec / 2) + threadIdx.x] =
+                            src[((size_t)(cZ0 + zr) * cR + cR0 + rr) * (kCellRec / 2) + threadIdx.x];
+        }
+        __syncthreads();
+        if (!live) return;
+        traj_run<DEPO, TRAJ, kTileNS>(a, sp, tc, i, x, N, steps, st);
+    } else if constexpr (MODE == kTrajLds) {
+        extern __shared__ __attribute__((aligned(16))) double s_coef[];
+        const int nodes = (a.g.nR + 2) * (a.g.nZ + 2);
+        for (int k = threadIdx.x; k < nodes * kTrajLdsNS; k += blockDim.x)
+            s_coef[k] = a.coef[(size_t)(k / kTrajLdsNS) * kNF + k % kTrajLdsNS];
+        __syncthreads();
+        if (!live) return;
+        traj_run<DEPO, TRAJ, kTrajLdsNS>(a, sp, (const double *)s_coef, i, x, N, steps, st);
+    } else {
+        if (!live) return;
+        traj_run<DEPO, TRAJ, kNF>(a, sp, (const double *)a.coef, i, x, N, steps, st);
+    }
+}
+
+template <int DEPO, bool TRAJ>
+__global__ void __launch_bounds__(64, TORJ_TRAJ_WAVES) k_traj(TraceArgs a, SplitArgs sp) {
+    traj_body<DEPO, TRAJ, kTrajL2>(a, sp);
+}
+template <int DEPO, bool TRAJ>
+__global__ void __launch_bounds__(512, TORJ_TRAJ_LDS_WAVES) k_traj_lds(TraceArgs a, SplitArgs sp) {
+    traj_body<DEPO, TRAJ, kTrajLds>(a, sp);
+}
+template <int DEPO, bool TRAJ>
+__global__ void __launch_bounds__(64, TORJ_TRAJ_TILE_WAVES) k_traj_tile(TraceArgs a, SplitArgs sp) {
+    traj_body<DEPO, TRAJ, kTrajTile>(a, sp);
+}
+// k_traj_cell is compiled in a translation unit of its own (torj_traj.hip)
+// without machine-level loop-invariant code motion: hoisted out of the step
+// loop, the kernel arguments' loads and constants held 208 VGPRs and spilled 15
+// SGPRs; left in place, 160 VGPRs and no spill, so two trajectory waves and two
+// 80-VGPR alpha waves share a SIMD.  The alpha kernel
+// keeps the hoisting (without it +3.4 % VALU and +49 % SALU).
+// TORJ_TRAJ_OWN_TU=1 (the Makefile, for torj_hip.hip): k_traj_cell is only
+// declared and comes from torj_traj.hip; 0 (torj_traj.hip itself, and a
+// single-TU build of torj_hip.hip): defined here.  That unit includes this
+// file without torj_k_fused.hpp, so the __constant__ tables c_gl, c_ts_a and
+// c_ts_bt exist in torj_hip.hip's unit alone -- a kernel that reads one belongs
+// in a header torj_traj.hip does not include.
+#ifndef TORJ_TRAJ_OWN_TU
+#define TORJ_TRAJ_OWN_TU 0
+#endif
+// measurement knob: a VGPR budget for the cell kernel between the 2- and 3-wave
+// bounds (176: two trajectory waves and two 80-VGPR alpha waves share a SIMD)
+#ifdef TORJ_TRAJ_CELL_VGPR
+#define TORJ_TRAJ_CELL_ATTR __attribute__((amdgpu_num_vgpr(TORJ_TRAJ_CELL_VGPR)))
+#else
+#define TORJ_TRAJ_CELL_ATTR
+#endif
+#if !TORJ_TRAJ_OWN_TU
+template <int DEPO, bool TRAJ>
+__global__ void __launch_bounds__(64, TORJ_TRAJ_TILE_WAVES) TORJ_TRAJ_CELL_ATTR k_traj_cell(TraceArgs a, SplitArgs sp) {
+    traj_body<DEPO, TRAJ, kTrajCell>(a, sp);
+}
+#else
+// defined and instantiated in torj_traj.hip (its own compile flags, above)
+template <int DEPO, bool TRAJ>
+__global__ void __launch_bounds__(64, TORJ_TRAJ_TILE_WAVES) TORJ_TRAJ_CELL_ATTR k_traj_cell(TraceArgs a, SplitArgs sp);
+#endif

@@ -982,10 +982,9 @@ TORJ_HD void series_pair_loop(double z, double &Sa, double &Sb) {
 // lanes that ran harmonic m's node loop, [4] waves and [5] live lanes of k_alpha_pts;
 // [6 ..] waves that reached a region of abs_albajar_fast_body (kAprof*)
 enum { kAprofTe = 6, kAprofPro, kAprofOk, kAprofH2, kAprofB2, kAprofH3, kAprofB3, kAprofZ, kAprofN = 14 };
-#ifdef TORJ_TRAJ_TU
-static
-#endif
-__device__ unsigned long long g_aprof[16];
+// (static: each translation unit that includes this header has its own; the
+// alpha kernels and the reader torj_alpha_prof_read share torj_hip.hip's)
+static __device__ unsigned long long g_aprof[16];
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TORJ_APROF_WAVE(K)                                                          \
     do {                                                                            \

@@ -1,9 +1,16 @@
 // torj_traj.hip -- the split pipeline's trajectory kernel k_traj_cell in a
 // translation unit of its own, compiled without machine-level loop-invariant
-// code motion (csrc/Makefile TRAJ_FLAGS): torj_hip.hip up to its trajectory
-// kernels, and their instances.  See the note at the top of torj_hip.hip.
-#define TORJ_TRAJ_TU 1
-#include "torj_hip.hip"
+// code motion (csrc/Makefile TRAJ_FLAGS; the note in torj_k_traj.hpp): the
+// trajectory kernels' header and the instances torj_hip.hip launches.
+#include <hip/hip_runtime.h>
+
+#include "torj_math.hpp"
+#include "torj_fitdepo.hpp"
+
+using namespace torj;
+
+#include "torj_args.hpp"
+#include "torj_k_traj.hpp"
 
 template __global__ void k_traj_cell<kDepoSamples, true>(TraceArgs, SplitArgs);
 template __global__ void k_traj_cell<kDepoSamples, false>(TraceArgs, SplitArgs);

@@ -30,7 +30,7 @@ def allreduce_deposition(dP_shell, group=None):
 def group_shard(n: int, n_shards: int, k: int) -> slice:
     """Shard k of n_shards over n rays with boundaries on 64-ray multiples (one
     wave / one work-queue group), as torj_trace_beam cuts a beam (beam_shard in
-    torj_hip.hip): every shard holds whole 64-ray groups of the unsplit beam, so
+    torj_beam.hpp): every shard holds whole 64-ray groups of the unsplit beam, so
     per-ray results do not depend on the split."""
     if n_shards < 1 or not (0 <= k < n_shards):
         raise ValueError(f"bad shard {k} / {n_shards}")
