@@ -4,7 +4,8 @@ a profiling build (python scripts/mkvariant.py aprof -DTORJ_ALPHA_PROF) counts,
 per harmonic, the waves that run the node loop and the lanes of those waves
 that need it, the waves / live lanes of the kernel, and the waves that reach
 each region of abs_albajar_fast_body (Te >= 20, the polarisation prologue,
-each harmonic past its exact-zero test and its skip bound).
+each harmonic past its exact-zero test and its skip bound, and harmonic 3
+dismissed from the prologue's outputs before either: h3_fast).
 usage: TORJ_HIP_LIB=.../libtorj_hip_aprof.so python tools/alpha_prof.py"""
 import ctypes
 import json
@@ -52,6 +53,9 @@ def main():
              "h3_not_zero", "h3_bound", "zero_flag_waves"]
     out["region_waves"] = {nm: v[6 + k] for k, nm in enumerate(names)}
     out["region_waves_per_kernel_wave"] = {nm: v[6 + k] / max(v[4], 1) for k, nm in enumerate(names)}
+    # harmonic 3: waves that dismissed it from the prologue's outputs (h3_fast_negligible)
+    # beside those that went on to its exact-zero test and its skip bound
+    out["harmonic3_waves"] = {"h3_fast": v[15], "h3_not_zero": v[11], "h3_bound": v[12]}
     # live lanes of the evaluated (not fully flagged) waves that carry a zero flag
     out["flagged_lanes_in_evaluated_waves"] = v[14]
     out["flagged_lane_fraction_of_evaluated"] = v[14] / max(v[5], 1)

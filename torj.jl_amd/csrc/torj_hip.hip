@@ -126,6 +126,10 @@ int torj_abs_al_init(int n) {
     // (torj_math.hpp albajar_harmonic); env TORJ_NEGL_SKIP=0 turns it off (A/B
     // and the test that holds both bit-identical), read at each abs_Al_init
     t.negl_skip = env_int("TORJ_NEGL_SKIP", 1) != 0;
+    // harmonic 3 dismissed from the prologue's outputs where its skip is certain
+    // (torj_math.hpp h3_fast_negligible; bit-identical, uncounted launches);
+    // env TORJ_H3_FAST=0 turns it off, and so does TORJ_NEGL_SKIP=0
+    t.h3_fast = t.negl_skip && env_int("TORJ_H3_FAST", 1) != 0;
     // the bounded skip of a harmonic whose share of alpha is provably below
     // tiny_alpha m^-1 (albajar_harmonic; ray tracing only -- the point entry
     // torj_abs_albajar_fast evaluates every harmonic): tau moves by less than

@@ -42,7 +42,9 @@
 // zero_box_flag proves from it that abs_albajar_fast_body returns +-0 at every
 // one of them -- all Te < 20 eV, or each harmonic m = 2, 3 absent (m Y <
 // sqrt(1 - N_par^2)) or an exact zero (every node's exp(mu (1 - gamma))
-// underflows: gamma_min > 1 + 760 / mu, with gamma_min >= m Y / (1 + |N_par|)
+// underflows: gamma_min > 1 + 760 / mu, the natural-exponent form of harm_geom's
+// ymax < kZeroYmax = -1096 in base 2 (torj_math.hpp; 760 log2(e) = 1096.4), with
+// gamma_min >= m Y / (1 + |N_par|)
 // on the resonance gamma - N_par u_par = m Y, |u_par| <= gamma) -- the early
 // settle of abs_albajar_fast_body (and its exact-zero test), which returns +0
 // there, decided for a whole block with relative margins of 1e-9 against

@@ -906,6 +906,7 @@ struct GLTable {
     int n;
     int negl_skip;  // 1: skip harmonic integrals provably below an ulp of the sum (default)
     double tiny_alpha;  // > 0: skip a harmonic whose rigorous bound on |alpha| is below it (m^-1)
+    int h3_fast;  // 1: dismiss harmonic 3 from the prologue's outputs where provably skipped (h3_fast_negligible)
     double t[kMaxGL], w[kMaxGL], st[kMaxGL], t2[kMaxGL];  // nodes, weights, sqrt(1-t^2), t^2
     // the node loop's per-node constants (pair_term), per harmonic m, one
     // 32-byte record per node (one scalar load of 8 dwords per pair): t, t^2,
@@ -980,8 +981,9 @@ TORJ_HD void series_pair_loop(double z, double &Sa, double &Sb) {
 #ifdef TORJ_ALPHA_PROF
 // profiling build only (tools/alpha_prof.py): [2 (m - 2)] waves and [2 (m - 2) + 1]
 // lanes that ran harmonic m's node loop, [4] waves and [5] live lanes of k_alpha_pts;
-// [6 ..] waves that reached a region of abs_albajar_fast_body (kAprof*)
-enum { kAprofTe = 6, kAprofPro, kAprofOk, kAprofH2, kAprofB2, kAprofH3, kAprofB3, kAprofZ, kAprofN = 14 };
+// [6 ..] waves that reached a region of abs_albajar_fast_body (kAprof*); [15] waves
+// that dismissed harmonic 3 by h3_fast_negligible
+enum { kAprofTe = 6, kAprofPro, kAprofOk, kAprofH2, kAprofB2, kAprofH3, kAprofB3, kAprofZ, kAprofN = 14, kAprofFast = 15 };
 // (static: each translation unit that includes this header has its own; the
 // alpha kernels and the reader torj_alpha_prof_read share torj_hip.hip's)
 static __device__ unsigned long long g_aprof[16];
@@ -1182,6 +1184,9 @@ TORJ_HD double node_sum(const GLTable &gl, const HarmConst &c, int sub = 0) {
 // whether the whole node sum underflows to an exact zero (albajar_harmonic).
 // Depends on (mu, r = m / m_0, N_par) only, so abs_albajar_fast_body computes it
 // before the polarisation vector and can settle alpha = 0 there.
+// The exact-zero threshold of a harmonic's largest node exponent (base 2; harm_geom,
+// h3_fast_negligible; torj_k_traj.hpp zero_box_flag restates it as 760 / mu).
+constexpr double kZeroYmax = -1096.0;
 struct HarmGeom {
     double r, r2m1, sq_r, upa0, upa1, C0, C1, C2, qmin;
     double Y0, Y1, ymax;  // TORJ_NODE_GAMMA_LIN: node exponents Y0 -+ Y1 t, their bound
@@ -1210,11 +1215,11 @@ TORJ_HD HarmGeom harm_geom(double mu, double inv_mu, double r, double Npar, doub
     g.Y1 = mu2 * (Npar * g.upa1);
     g.ymax = g.Y0 + fabs(g.Y1);
     // Exact zero: every node's 2^y underflows to +0 (exp2_node returns exactly 0
-    // below y = -1076) when ymax < -1096 -- round 3's mu (gamma_min - 1) > 760 in
+    // below y = -1076) when ymax < kZeroYmax = -1096 -- round 3's mu (gamma_min - 1) > 760 in
     // base 2, whose margin covers the roundings of ymax and of each node's y (a
     // few 1e-13).  Then the node sum is +-0 and the loop is skipped with the same
     // value; NaN operands never skip.
-    g.zero = g.ymax < -1096.0;
+    g.zero = g.ymax < kZeroYmax;
     g.C0 = g.C1 = g.C2 = g.qmin = 0.0;  // (the square-root form's, unused)
     (void)inv_mu;
 #else
@@ -1257,14 +1262,11 @@ struct AlbajarWork {
     uint32_t n_early;   // exact-zero harmonics of calls settled before the polarisation vector / -
 };
 
-// Resonance-ellipse integral for harmonic m (abs_Al_integral_nume_fast +
-// abs_Al_pol_fact) times sqrt((m/m_0)^2 - 1), WITHOUT the Maxwellian
-// normalisation a*(mu/2pi)^1.5 (common to both harmonics).
-template <int M, int LPR = 1, int U = TORJ_PAIR_UNROLL>
-TORJ_HD double albajar_harmonic(const GLTable &gl, double mu, const HarmGeom &hg,
-                                double inv_sqNp, double N_perp, double omega_bar,
-                                double Axz, double ea, double e3, AlbajarWork *work, int sub = 0,
-                                double dom = 0.0, double hmax = 0.0) {
+// Harmonic m's constants of the node sum from its geometry and the polarisation
+// vector (albajar_harmonic).
+template <int M>
+TORJ_HD HarmConst harm_consts(double mu, const HarmGeom &hg, double inv_sqNp, double N_perp,
+                              double omega_bar, double Axz, double ea, double e3) {
     constexpr double md = (double)M, inv_md = 1.0 / md;
     HarmConst c;
     c.r2m1 = hg.r2m1;
@@ -1290,7 +1292,59 @@ TORJ_HD double albajar_harmonic(const GLTable &gl, double mu, const HarmGeom &hg
     c.Y1 = hg.Y1;
     c.hx = 0.5 * c.x_m;
     c.hx2 = c.hx * c.hx;
-    const double qmin = hg.qmin;
+    return c;
+}
+
+// B0 of albajar_harmonic's skip tests: |harmonic m's integral| <= B0 E_max (the
+// derivation stands at its use), Pm = m / (N_perp omega_bar)
+template <int M>
+TORJ_HD double harm_b0(const HarmConst &c, double mu, double Pm, double sq_r) {
+    constexpr double iS = inv_fact(M), iS1 = inv_fact(M + 1), iSl = inv_fact(M - 1);
+    const double hx = c.hx, hx2 = hx * hx;
+    const double A = hx * (iS * iS), T1 = hx2 * iS1;
+    const double Bv = fabs(c.K2) * iSl * hx * T1, Cc = iS * (iSl + T1);
+    const double Pmax = A * (fabs(c.K0) + fabs(c.K3)) + Cc * fabs(c.K1) + Bv;
+    const double Qmax = A * fabs(c.K4) + Cc * fabs(c.K5);
+    double p = hx;  // hx^(2m-1)
+#pragma unroll
+    for (int k = 1; k < 2 * M - 1; k++) p *= hx;
+    return 4.0 * mu * (Pm * Pm) * sq_r * p * (Pmax + Qmax);
+}
+
+// E_max of the same tests, an upper bound on every node's exp(mu (1 - gamma))
+TORJ_HD double harm_emax(const HarmGeom &hg, const HarmConst &c, double mu) {
+#if TORJ_NODE_GAMMA_LIN
+    // E_max <= 2^(ceil(ymax) + 1): every node's y is at most ymax up to its
+    // roundings (a few 1e-13), the extra factor 2 covers them and exp2_node's
+    // 4e-12; a NaN ymax gives an infinite bound, which never skips
+    const double yb = ceil(hg.ymax) + 1.0;
+    const double Emax = ldexp_i(1.0, (int)fmax(fmin(yb, 2000.0), -2000.0));
+#elif TORJ_EMAX_BOUND
+    // an upper bound on E_max = exp(mu (1 - gamma_min)) without the exponential:
+    // 2^(ceil(y) + 1) with y = mu log2(e) (1 - gamma_min) from the node loop's
+    // square root (a few ulp; the extra factor 2 covers y's rounding, |y| <
+    // 2^16), so the bound stays rigorous with at most 4x of slack; a NaN y
+    // gives an infinite bound (fmin / fmax return the non-NaN operand), which
+    // never skips
+    const double yb = ceil(c.mu2 * (1.0 - sqrt_node(hg.qmin))) + 1.0;
+    const double Emax = ldexp_i(1.0, (int)fmax(fmin(yb, 2000.0), -2000.0));
+#else
+    const double Emax = exp_fast<true>(mu * (1.0 - sqrt_nn(hg.qmin)));
+#endif
+    return Emax;
+}
+
+// Resonance-ellipse integral for harmonic m (abs_Al_integral_nume_fast +
+// abs_Al_pol_fact) times sqrt((m/m_0)^2 - 1), WITHOUT the Maxwellian
+// normalisation a*(mu/2pi)^1.5 (common to both harmonics).
+template <int M, int LPR = 1, int U = TORJ_PAIR_UNROLL>
+TORJ_HD double albajar_harmonic(const GLTable &gl, double mu, const HarmGeom &hg,
+                                double inv_sqNp, double N_perp, double omega_bar,
+                                double Axz, double ea, double e3, AlbajarWork *work, int sub = 0,
+                                double dom = 0.0, double hmax = 0.0) {
+    constexpr double md = (double)M;
+    const HarmConst c = harm_consts<M>(mu, hg, inv_sqNp, N_perp, omega_bar, Axz, ea, e3);
+    const double sq_r = hg.sq_r;
     const bool zero = hg.zero;  // the exact-zero bound (harm_geom)
     // Bessel polynomial from the largest argument x_m (SeriesCoefs: x_m <= 1,
     // 2, 3, 4, each within a few ulp of mpmath's J_nu, checked in tests; the
@@ -1330,36 +1384,9 @@ TORJ_HD double albajar_harmonic(const GLTable &gl, double mu, const HarmGeom &hg
     const bool rel = gl.negl_skip && dom != 0.0 && fabs(dom) < INFINITY && fabs(dom) > 1e-290;
     if (rel || hmax > 0.0) {
         TORJ_APROF_WAVE(M == 2 ? kAprofB2 : kAprofB3);
-        constexpr double iS = inv_fact(M), iS1 = inv_fact(M + 1), iSl = inv_fact(M - 1);
-        const double hx = c.hx, hx2 = hx * hx;
-        const double A = hx * (iS * iS), T1 = hx2 * iS1;
-        const double Bv = fabs(c.K2) * iSl * hx * T1, Cc = iS * (iSl + T1);
-        const double Pmax = A * (fabs(c.K0) + fabs(c.K3)) + Cc * fabs(c.K1) + Bv;
-        const double Qmax = A * fabs(c.K4) + Cc * fabs(c.K5);
-        double p = hx;  // hx^(2m-1)
-#pragma unroll
-        for (int k = 1; k < 2 * M - 1; k++) p *= hx;
-        const double B0 = 4.0 * mu * (Pm * Pm) * sq_r * p * (Pmax + Qmax);
+        const double B0 = harm_b0<M>(c, mu, Pm, sq_r);
         const double R = B0 * rcp_nz(fabs(dom));
-#if TORJ_NODE_GAMMA_LIN
-        // E_max <= 2^(ceil(ymax) + 1): every node's y is at most ymax up to its
-        // roundings (a few 1e-13), the extra factor 2 covers them and exp2_node's
-        // 4e-12; a NaN ymax gives an infinite bound, which never skips
-        const double yb = ceil(hg.ymax) + 1.0;
-        const double Emax = ldexp_i(1.0, (int)fmax(fmin(yb, 2000.0), -2000.0));
-        (void)qmin;
-#elif TORJ_EMAX_BOUND
-        // an upper bound on E_max = exp(mu (1 - gamma_min)) without the exponential:
-        // 2^(ceil(y) + 1) with y = mu log2(e) (1 - gamma_min) from the node loop's
-        // square root (a few ulp; the extra factor 2 covers y's rounding, |y| <
-        // 2^16), so the bound stays rigorous with at most 4x of slack; a NaN y
-        // gives an infinite bound (fmin / fmax return the non-NaN operand), which
-        // never skips
-        const double yb = ceil(c.mu2 * (1.0 - sqrt_node(qmin))) + 1.0;
-        const double Emax = ldexp_i(1.0, (int)fmax(fmin(yb, 2000.0), -2000.0));
-#else
-        const double Emax = exp_fast<true>(mu * (1.0 - sqrt_nn(qmin)));
-#endif
+        const double Emax = harm_emax(hg, c, mu);
         // R, B0 < 1e300: an E_max that underflowed to 0 cannot hide a huge bound
         if ((rel && R < 1e300 && R * Emax < 0x1p-58) || (B0 < 1e300 && B0 * Emax < hmax)) {
             if (work) work->n_negl++;
@@ -1537,6 +1564,61 @@ TORJ_HD double tiny_harmonic(double tiny_alpha, const AlbPro &q, double X, doubl
     return h < INFINITY ? h : 0.0;
 }
 
+// Harmonic 3 dismissed from the prologue's outputs alone (GLTable::h3_fast): an
+// upper bound U on twice albajar_harmonic<3>'s B0 and an upper bound y_ub on
+// harm_geom(3)'s ymax, with no square root, no reciprocal, no HarmGeom, HarmConst
+// or Bessel level, and no branch.  With s = 1 / sqrt(1 - N_par^2), r = 3 / m_0,
+// xi = N_perp s:
+//  * sqrt(r^2 - 1) <= r, so x_3 / 3 <= N_perp omega_bar r / 3 = xi, hx <= h = 1.5 xi,
+//    q <= xi s, and Pm hx = 1.5 sqrt(r^2 - 1) exactly (no quotient by N_perp omega_bar):
+//    B0 = 4 mu Pm^2 sq_r hx^5 (Pmax + Qmax) <= 9 mu r^3 h^3 (Pmax + Qmax);
+//  * with S = |Axz| + |ea| + |e3| (1 + xi s), at least each of |Axz|, |ea|, |e3|
+//    and q |e3| (a sum, not a maximum: a NaN term makes it NaN): |K0| <= 2 S^2,
+//    |K1|, |K5| <= S^2 xi, |K2| <= 4/9 S^2, |K3| <= S^2, |K4| <= 2 S^2, so
+//    Pmax + Qmax <= S^2 (5 h / 36 + h^3 / 108 + (1/2 + h^2 / 24) xi / 3)
+//                 = S^2 xi (3/8 + xi^2 / 16);
+//  * U is 4 times that product, mu r^3 xi^4 S^2 (45.5625 + 7.59375 xi^2): the 2
+//    the test asks for and 2 for the ~30 roundings of both sides (a few 1e-15);
+//  * ymax = mu2 (1 - r s + |N_par| s sqrt(r^2 - 1)) <= mu2 (1 - r s (1 - |N_par|))
+//    (gamma_min >= 3 Y / (1 + |N_par|)), taken with a relative 1e-13 on both
+//    terms against the ~1e-15 of ymax's and its own roundings.
+// Refuses (false; U and y_ub then mean nothing) whenever albajar_harmonic could
+// return anything but a zero or the bounds' roundings could not be trusted:
+// N_perp or omega_bar not finite and positive (an infinite Pm turns the exact
+// zero into NaN), r^2 - 1 not safely positive (a NaN square root integrates),
+// any operand NaN (every comparison below fails on one) or outside ranges that
+// keep every product above in the normal range, U >= 1e300.
+TORJ_HD bool h3_fast_bound(const AlbPre &pre, const AlbPro &q, double N_par, double &U, double &y_ub) {
+    const double s = pre.inv_sqNp, xi = pre.N_perp * s, r = 3.0 * pre.inv_m0, xi2 = xi * xi;
+    const double S = fabs(q.Axz) + fabs(q.ea) + fabs(q.e3) * fma(xi, s, 1.0);
+    U = pre.mu * (r * r * r) * (xi2 * xi2) * (S * S) * fma(7.59375, xi2, 45.5625);
+    const double wn = (1.0 - fabs(N_par)) - 1e-13;
+    y_ub = (pre.mu * 1.4426950408889634074) * fma(-(r * s), wn, 1.0 + 1e-13);
+    // (&, not &&: one chain of compares instead of a branch per term)
+    return (pre.omega_bar >= 1e-30) & (pre.omega_bar <= 1e30) & (pre.mu >= 1e-30) & (s <= 1e30) &
+           (xi >= 1e-30) & (xi <= 1e30) & (r >= 1.0 + 1e-12) & (r <= 1e30) & (S >= 1e-30) & (S <= 1e60) &
+           (U < 1e300);
+}
+// 2^(ceil(y_ub) + 1) >= albajar_harmonic's E_max, kept above 2^-1000 so that a
+// bound times it cannot vanish beside a huge quotient by |dom|
+TORJ_HD double h3_fast_emax(double y_ub) {
+    return ldexp_i(1.0, (int)fmax(fmin(ceil(y_ub) + 1.0, 2000.0), -1000.0));
+}
+// True only when albajar_harmonic<3> would return a zero at this point: its
+// exact zero (y_ub < kZeroYmax, hence ymax), or one of its two skips,
+//   U 2^(ceil(y_ub) + 1) < hmax (hmax > 0),  U 2^(ceil(y_ub) + 1) < 2^-58 |dom| (rel),
+// which imply B0 E_max < hmax and R E_max < 2^-58 with R < 1e300 (U >= 2 B0,
+// the power of two >= 2^-1000, rounding monotone).  The left sides are never
+// negative, so hmax <= 0 and dom = 0 fail by themselves.  dom: the harmonics
+// summed so far; rel as in albajar_harmonic with negl_skip on (h3_fast implies it).
+TORJ_HD bool h3_fast_negligible(const AlbPre &pre, const AlbPro &q, double N_par, double hmax, double dom) {
+    double U, y_ub;
+    const bool ok = h3_fast_bound(pre, q, N_par, U, y_ub);
+    const double B = U * h3_fast_emax(y_ub), ad = fabs(dom);
+    const bool rel = (ad < INFINITY) & (ad > 1e-290);
+    return ok & ((y_ub < kZeroYmax) | (B < hmax) | (rel & (B < 0x1p-58 * ad)));
+}
+
 template <int LPR = 1, int U = TORJ_PAIR_UNROLL>
 TORJ_HD double abs_albajar_fast_body(const GLTable &gl, double omega, double X, double Y,
                                      double N_abs, double N_par, double Te, int mode,
@@ -1547,7 +1629,6 @@ TORJ_HD double abs_albajar_fast_body(const GLTable &gl, double omega, double X, 
     const bool h2 = !(2.0 < pre.m_0), h3 = !(3.0 < pre.m_0);  // harmonic m present iff m >= m_0
     HarmGeom g2{}, g3{};
     if (h2) g2 = harm_geom(pre.mu, pre.inv_mu, 2.0 * pre.inv_m0, N_par, pre.inv_sqNp);
-    if (h3) g3 = harm_geom(pre.mu, pre.inv_mu, 3.0 * pre.inv_m0, N_par, pre.inv_sqNp);
     // Settled before the polarisation vector: when every harmonic present is an
     // exact zero (harm_geom), alpha is a zero whatever the polarisation -- the
     // harmonics would return -mu Pm^2 0 sq_r, finite and zero because N_perp and
@@ -1556,9 +1637,18 @@ TORJ_HD double abs_albajar_fast_body(const GLTable &gl, double omega, double X, 
     // K coefficients and the normalisation are skipped (44 % of the stage points
     // of the headline beam: edge plasma and far from every resonance).  Off with
     // the negligible-harmonic skip (GLTable::negl_skip, TORJ_NEGL_SKIP=0).
-    if (gl.negl_skip && pre.N_perp > 0.0 && pre.N_perp < INFINITY && pre.omega_bar > 0.0 &&
-        pre.omega_bar < INFINITY && pre.mu < INFINITY &&
-        (!h2 || (g2.zero && g2.sq_r < INFINITY)) && (!h3 || (g3.zero && g3.sq_r < INFINITY))) {
+    // Harmonic 3's geometry is built here only if a lane of the wave can still
+    // settle (everything but g3 says so); otherwise where harmonic 3 is taken.
+    const bool settle2 = gl.negl_skip && pre.N_perp > 0.0 && pre.N_perp < INFINITY && pre.omega_bar > 0.0 &&
+                         pre.omega_bar < INFINITY && pre.mu < INFINITY &&
+                         (!h2 || (g2.zero && g2.sq_r < INFINITY));
+#ifdef __HIP_DEVICE_COMPILE__
+    const bool early3 = __any(settle2 && h3) != 0;
+#else
+    const bool early3 = settle2 && h3;
+#endif
+    if (early3 && h3) g3 = harm_geom(pre.mu, pre.inv_mu, 3.0 * pre.inv_m0, N_par, pre.inv_sqNp);
+    if (settle2 && (!h3 || (g3.zero && g3.sq_r < INFINITY))) {
         if (work) work->n_early += (uint32_t)h2 + (uint32_t)h3;
         return 0.0;
     }
@@ -1570,7 +1660,25 @@ TORJ_HD double abs_albajar_fast_body(const GLTable &gl, double omega, double X, 
     const double hmax = tiny_harmonic(tiny, q, X, omega);
     double c_abs = 0.0;
     if (h2) c_abs += albajar_pro_harmonic<2, LPR, U>(gl, q, g2, work, sub, 0.0, hmax);
-    if (h3) c_abs += albajar_pro_harmonic<3, LPR, U>(gl, q, g3, work, sub, c_abs, hmax);
+    if (h3) {
+        // Harmonic 3 dismissed for the whole wave or not at all (uncounted
+        // launches): albajar_harmonic's level ballot lets a skipping lane raise an
+        // integrating lane's polynomial length, so a per-lane shortcut would
+        // change other lanes' bits.  c_abs + (+-0) is c_abs: bit-identical.
+        bool fast = false;
+        if (!work && gl.h3_fast && gl.negl_skip) {
+            fast = h3_fast_negligible(pre, q, N_par, hmax, c_abs);
+#ifdef __HIP_DEVICE_COMPILE__
+            fast = __all(fast) != 0;
+#endif
+        }
+        if (fast) {
+            TORJ_APROF_WAVE(kAprofFast);
+        } else {
+            if (!early3) g3 = harm_geom(pre.mu, pre.inv_mu, 3.0 * pre.inv_m0, N_par, pre.inv_sqNp);
+            c_abs += albajar_pro_harmonic<3, LPR, U>(gl, q, g3, work, sub, c_abs, hmax);
+        }
+    }
     return albajar_finish(q, c_abs, X, omega);
 }
 // the fused trace kernels' call (out of line there, see TORJ_ALB_ATTR); kernels

@@ -9,6 +9,12 @@ evaluations, absorption calls that reach the harmonic sum, harmonic integrals,
 Bessel-series terms), so the per-launch figure is exact for the branches
 actually taken.  Absorption calls that exit early (Te < 20 eV, N outside (0,1],
 X >= 1) are counted as zero work (conservative).
+
+Counted launches always take albajar_harmonic's own path, so they price the
+full bound (FLOPS_HARM + FLOPS_NEGL_TEST) for third-harmonic integrals that
+timed launches dismiss more cheaply from the prologue's outputs (torj_math.hpp
+h3_fast_negligible, GLTable::h3_fast): the counted `frac` is slightly high, and
+`frac_executed` (from the executed-instruction counters) is the figure to follow.
 """
 from __future__ import annotations
 
