@@ -48,6 +48,9 @@ struct TraceArgs {
     int n_hist, hist_off;
 };
 
+// the adaptive queue kernel's Tsit5 stage vectors in dynamic LDS (k_trace_sched)
+constexpr int kTsLds = 7 * 7 * 64;  // doubles per wave
+
 // DEPO modes of the trace kernels
 constexpr int kDepoNone = 0, kDepoBinned = 1, kDepoSamples = 2;
 

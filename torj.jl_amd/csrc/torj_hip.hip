@@ -11,10 +11,12 @@
 //   torj_host_util.hpp  fail / HIPCK, the environment knobs, GrowBuf
 //   torj_plasma.hpp     the plasma handle and its device state
 //   torj_fan.hpp        quadrature nodes and the launch fan
+//   torj_dispatch.hpp   run-time (absorption, deposition, trajectory) -> kernel instance
 //   torj_split.hpp      the split pipeline's launches (split_trace)
+//   torj_launch.hpp     one launch of the hot path: LaunchPlan, FitLayout,
+//                       trace_device_one, trace_batched, the Gauss-Legendre upload
 //   torj_beam.hpp       torj_trace_beam's multi-device layer
-// Here: the Gauss-Legendre table's upload, trace_device_one (one launch of the
-// hot path) and the extern "C" functions.
+// Here: the Gauss-Legendre table's construction and the extern "C" functions.
 // k_traj_cell is compiled in torj_traj.hip with flags of its own (-DTORJ_TRAJ_OWN_TU=1
 // here, csrc/Makefile); without that define this file is the whole library.
 #include <hip/hip_runtime.h>
@@ -44,30 +46,8 @@ using namespace torj;
 #include "torj_plasma.hpp"
 #include "torj_fan.hpp"
 #include "torj_split.hpp"
+#include "torj_launch.hpp"
 #include "torj_beam.hpp"
-
-// ===========================================================================
-// Gauss-Legendre table (abs_Al_init, src/absorption.jl:1-7): the host copy and
-// its upload into c_gl (torj_k_fused.hpp), once per device and version
-// ===========================================================================
-static std::mutex g_gl_mu;
-static GLTable g_gl_host;
-static int g_gl_version = 0;         // 0: abs_Al_init never called
-static int g_gl_uploaded[64] = {0};  // per device
-
-static int ensure_gl_on_device(int dev) {
-    std::lock_guard<std::mutex> lk(g_gl_mu);
-    if (g_gl_version == 0)
-        return fail(
-            "The weights and abscissae for the absorption were never initialized. Call "
-            "`abs_Al_init` before using the absorption.");
-    if (dev < 0 || dev >= 64) return fail("device index %d out of range", dev);
-    if (g_gl_uploaded[dev] != g_gl_version) {
-        HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(c_gl), &g_gl_host, sizeof(GLTable)));
-        g_gl_uploaded[dev] = g_gl_version;
-    }
-    return 0;
-}
 
 // ===========================================================================
 // C ABI
@@ -545,308 +525,6 @@ int torj_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const d
                                 status, steps, dP, Pdep, traj, counters, stream);
 }
 
-}  // extern "C"
-
-// one launch of the hot path over n rays (the body of torj_trace_device_ex)
-static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
-                            const double *N0, const double *weights, int n_psi, const double *grid,
-                            const double *x_launch, const double *s0, double *state, int *status,
-                            int *steps, double *dP, double *Pdep, double *traj, uint64_t *counters,
-                            void *stream) {
-    if (n <= 0) return 0;
-    if (!x0 || !N0 || !state || !status || !steps) return fail("x0, N0, state, status, steps required");
-    if (cfg->n_steps < 0) return fail("n_steps < 0");
-    if (cfg->mode != 1 && cfg->mode != -1) return fail("mode must be +1 (X) or -1 (O)");
-    if (!(cfg->ds > 0)) return fail("ds must be > 0");
-    if (cfg->deposition != 0 && cfg->deposition != 1) return fail("deposition must be 0 or 1");
-    if (cfg->integrator != 0 && cfg->integrator != 1) return fail("integrator must be 0 or 1");
-    if (cfg->integrator == 1 && (!(cfg->s_max > 0) || cfg->n_chunks < 1 || !(cfg->abstol > 0) ||
-                                 !(cfg->reltol > 0) || cfg->n_steps < 1))
-        return fail("integrator 1 needs s_max > 0, n_chunks >= 1, abstol, reltol > 0, n_steps >= 1");
-    const bool depo = n_psi >= 2 && grid && dP;
-    const bool fit = depo && cfg->deposition == 1;
-    if (fit && (!x_launch || !s0))
-        return fail("deposition = 1 (reference profile) needs x_launch and s0 (torj_trace_ex)");
-    const bool tr = cfg->traj_stride > 0 && traj;
-    if (ensure_device(p)) return -1;
-    if (cfg->absorption < 0 || cfg->absorption > 3) return fail("absorption must be 0..3");
-    if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    TraceArgs a{};
-    a.coef = p->d_coef;
-    a.cellp = p->d_cellp;
-    a.g = p->g;
-    a.k = make_consts(cfg->omega);
-    a.omega = cfg->omega;
-    a.mode = cfg->mode;
-    a.ds = cfg->ds;
-    a.n_steps = cfg->n_steps;
-    a.chunk_steps = cfg->chunk_steps;
-    a.psi_exit = cfg->psi_exit;
-    a.P_min = cfg->P_min;
-    a.n = n;
-    a.x0 = x0;
-    a.N0 = N0;
-    a.w = weights;
-    a.state = state;
-    a.status = status;
-    a.steps = steps;
-    a.counters = (unsigned long long *)counters;
-    a.s0 = s0;
-    a.abs_model = cfg->absorption;
-    if (cfg->integrator == 1) {
-        a.abstol = cfg->abstol;
-        a.reltol = cfg->reltol;
-        a.s_step = cfg->s_max / cfg->n_chunks;
-        a.n_chunks = cfg->n_chunks;
-        if (ensure_chunks(p, (size_t)n)) return -1;
-        a.chunk = (int *)p->chunk.d;
-    }
-    if (depo) {
-        a.n_psi = n_psi;
-        a.grid = grid;  // uniform-grid fast path is set up in-kernel from grid[0], grid[n-1]
-        a.dP = dP;
-        if (!Pdep) {  // the work-queue kernel carries P_dep across chunks: workspace
-            if (ensure_workspace(p, (size_t)n)) return -1;
-            Pdep = (double *)p->ws.d;
-        }
-        a.Pdep = Pdep;
-    }
-    FitArgs fa{};
-    if (fit) {
-        // samples (psi, dP/ds) per step, Thomas/second-derivative arrays,
-        // per-boundary root counts, per-shell open-root integrals
-        const size_t K = (size_t)cfg->n_steps + 2, N = (size_t)n, L = (size_t)n_psi;
-        const size_t KN = smp_elems(N, K);  // smp_at layout: 64-ray blocks of K rows
-        // arc lengths are stored by the adaptive integrator only (RK4: s0 + k ds)
-        const size_t n_smp = cfg->integrator == 1 ? 3 : 2;
-        const size_t b_smp = n_smp * KN * sizeof(double), b_m = 3 * KN * sizeof(double);
-        const size_t b_cnt = ((L + 1) * N * sizeof(int) + 255) & ~(size_t)255, b_fo = L * N * sizeof(double);
-        const size_t b_ks = (N * sizeof(int) + 255) & ~(size_t)255;
-        if (ensure_fit(p, b_smp + b_m + b_cnt + 2 * b_fo + b_ks)) return -1;
-        char *base = (char *)p->fit.d;
-        a.smp_psi = (double *)base;
-        a.smp_dpds = a.smp_psi + KN;
-        a.smp_s = cfg->integrator == 1 ? a.smp_dpds + KN : nullptr;
-        a.smp_rows = K;
-        fa.rows = K;
-        fa.E = (double *)(base + b_smp);
-        fa.Gpsi = fa.E + KN;
-        fa.GP = fa.Gpsi + KN;
-        fa.cnt = (int *)(base + b_smp + b_m);
-        fa.Fopen = (double *)(base + b_smp + b_m + b_cnt);
-        fa.dPs = fa.Fopen + L * N;
-        fa.kstar = (int *)(base + b_smp + b_m + b_cnt + 2 * b_fo);
-        // (the walk's per-boundary / per-shell arrays are cleared by fit_zero:
-        // on the split path on its scan stream, beside the first trajectory
-        // block, else on `s` before the trace)
-        fa.coef = p->d_coef;
-        fa.g = p->g;
-        fa.n = n;
-        fa.n_psi = n_psi;
-        fa.ds = cfg->ds;
-        fa.grid = grid;
-        fa.w = weights;
-        fa.x_launch = x_launch;
-        fa.s0 = s0;
-        fa.steps = steps;
-        fa.smp_psi = a.smp_psi;
-        fa.smp_dpds = a.smp_dpds;
-        fa.smp_s = a.smp_s;
-        fa.s_uniform = cfg->integrator == 0;  // RK4: s_k = s0 + k ds, not stored
-        fa.dP = dP;
-        fa.Pray = Pdep;
-        // boundary lookups guess from grid[0], grid[n-1] in-kernel and correct
-        // locally: no host read of the (device-resident) grid, no stream sync
-    }
-    if (depo)  // psi_dP_dV strictly increasing: checked on the device, reported by torj_trace_check
-        hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
-    const int DM = !depo ? kDepoNone : (fit ? kDepoSamples : kDepoBinned);
-    DepoStream dstr{};  // the split pipeline's streamed deposition (split_trace)
-    if (tr) {
-        a.traj_stride = cfg->traj_stride;
-        a.n_save = cfg->n_steps / cfg->traj_stride;
-        a.traj = traj;
-        if (a.n_save > 0)
-            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * n * sizeof(double), s));  // NaN
-    }
-    static const int sched_env = env_int("TORJ_SCHED", 1);
-    const int G = (n + TORJ_GROUP - 1) / TORJ_GROUP;
-    const int cs = cfg->chunk_steps > 0 ? cfg->chunk_steps : std::max(cfg->n_steps, 1);
-    // default: the queue pays off once the beam exceeds one wave per SIMD
-    // (measured: 42k rays 111 vs 106 ms one-shot; 100k rays 151 vs 174 ms)
-    const bool adaptive = cfg->integrator == 1;
-    const int use_sched = adaptive || cfg->absorption >= 2
-                              ? 1  // the adaptive path runs one tspan chunk per visit; warm always queues
-                                   : p->sched_mode >= 0 ? p->sched_mode
-                                                        : (sched_env && G > p->n_cu * 4 ? 1 : 0);
-// every <absorption, deposition mode, trajectory> instance of a trace kernel
-// (warm models: the TRAJ instance only, with traj_stride = 0 when no
-// trajectory is wanted -- fewer instances of the heavy warm code)
-#define TORJ_DISPATCH_T(L, A, D)            \
-    do {                                    \
-        if (tr)                             \
-            L(A, D, true);                  \
-        else                                \
-            L(A, D, ((A) >= 2 ? true : false)); \
-    } while (0)
-#define TORJ_DISPATCH_D(L, A)                                 \
-    do {                                                      \
-        if (DM == kDepoBinned)                                \
-            TORJ_DISPATCH_T(L, A, kDepoBinned);               \
-        else if (DM == kDepoSamples)                          \
-            TORJ_DISPATCH_T(L, A, kDepoSamples);              \
-        else                                                  \
-            TORJ_DISPATCH_T(L, A, kDepoNone);                 \
-    } while (0)
-#define TORJ_DISPATCH_TRACE(L)              \
-    do {                                    \
-        if (cfg->absorption == 3)           \
-            TORJ_DISPATCH_D(L, 3);          \
-        else if (cfg->absorption == 2)      \
-            TORJ_DISPATCH_D(L, 2);          \
-        else if (cfg->absorption == 1)      \
-            TORJ_DISPATCH_D(L, 1);          \
-        else                                \
-            TORJ_DISPATCH_D(L, 0);          \
-    } while (0)
-// the one-lane-per-ray kernel: cold and Albajar only (warm always queues)
-#define TORJ_DISPATCH_TRACE01(L)            \
-    do {                                    \
-        if (cfg->absorption == 1)           \
-            TORJ_DISPATCH_D(L, 1);          \
-        else                                \
-            TORJ_DISPATCH_D(L, 0);          \
-    } while (0)
-    static const int split_env = env_int("TORJ_SPLIT", 1);
-    static const int split_warm_env = env_int("TORJ_SPLIT_WARM", -1);  // -1 auto, 0 off, 1 on
-    // the split RK4 path (fixed steps; sched mode 3 forces it):
-    //  * Albajar: by default for beams that would use the work queue;
-    //  * warm weakly relativistic (2): by default -- its alpha kernel runs two
-    //    waves per SIMD where the fused queue kernel holds one (C5: 165 vs 221 ms);
-    //  * warm fully relativistic (3): by default for beams of fewer 64-ray groups
-    //    than 3 per CU, where the one-wave-per-SIMD queue kernel leaves SIMDs idle
-    //    and the split's alpha kernel spreads the points over all of them (129
-    //    rays: 13.1 s -> 0.1 s); on the 1e5-ray fan the queue kernel is faster
-    //    (19.7 vs 20.4 s)
-    const bool albajar_split = cfg->absorption == 1 && split_env == 1 && sched_env && G > p->n_cu * 4;
-    const bool warm_split = cfg->absorption >= 2 && split_env == 1 &&
-                            (split_warm_env == 1 ||
-                             (split_warm_env < 0 && (cfg->absorption == 2 || G < p->n_cu * 3)));
-    // (the split kernels pack a ray's step count into 24 bits beside its status)
-    const bool use_split = !adaptive && cfg->absorption >= 1 && cfg->n_steps > 0 &&
-                           cfg->n_steps < kSplitMaxSteps &&
-                           (p->sched_mode == 3 || (p->sched_mode < 0 && (albajar_split || warm_split)));
-    // the fused / queue paths clear the deposition workspace before the trace
-    // phase's first event (outside trace_ms, as before round 5); the split path
-    // clears it on its scan stream, overlapped with the first trajectory block
-    if (fit && !use_split && fit_zero(fa, s)) return -1;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (p->timing) {
-        if (p->ev_used + 3 > p->ev_pool.size()) {
-            for (int q = 0; q < 3; q++) {
-                hipEvent_t e;
-                HIPCK(hipEventCreate(&e));
-                p->ev_pool.push_back(e);
-            }
-        }
-        for (int q = 0; q < 3; q++) ev[q] = p->ev_pool[p->ev_used + q];
-        p->ev_used += 3;
-        HIPCK(hipEventRecord(ev[0], s));
-    }
-    if (use_split) {
-        if (split_trace(p, a, DM, tr, s, fit ? &fa : nullptr, &dstr, g_gl_host.negl_skip != 0)) return -1;
-    } else if (use_sched && cfg->n_steps > 0) {
-        // W persistent waves: at most 2 per SIMD (4 SIMDs per CU), and fewer
-        // than G so the ready queue keeps a backlog (a wave never waits for a
-        // group while another holds it); TORJ_SCHED_W overrides.
-        static const int w_env = env_int("TORJ_SCHED_W", 0);
-        int W = p->sched_waves > 0 ? p->sched_waves
-                : w_env > 0        ? w_env
-                                   : std::min(p->n_cu * 4 * (cfg->absorption >= 2 ? TORJ_WARM_MIN_WAVES
-                                                                                  : TORJ_MIN_WAVES),
-                                              G - G / 16);
-        W = std::max(1, std::min(W, G));
-        const unsigned S = 4u * (unsigned)(G + W);  // ring slots (tag check makes reuse safe)
-        const size_t bytes = 256 + (size_t)S * sizeof(unsigned long long);
-        if (ensure_sched(p, bytes)) return -1;
-        HIPCK(hipMemsetAsync(p->sched.d, 0, bytes, s));
-        SchedCtl *ctl = (SchedCtl *)p->sched.d;
-        unsigned long long *slots = (unsigned long long *)((char *)p->sched.d + 256);
-        const dim3 grd(W), blk(64);
-        // binned shells: a per-wave LDS histogram (RK4, up to 4096 shells; the
-        // adaptive path's 25 KB of stage vectors leave no room without losing
-        // occupancy, it keeps the global atomics)
-        a.hist_off = adaptive ? kTsLds : 0;
-        a.n_hist = (DM == kDepoBinned && !adaptive && n_psi <= 4096) ? n_psi : 0;
-        const size_t lds = (size_t)(a.hist_off + a.n_hist) * sizeof(double);
-#define LAUNCH(A, D, T)                                                                            \
-    do {                                                                                           \
-        if (adaptive)                                                                              \
-            hipLaunchKernelGGL((k_trace_sched<A, D, T, 1>), grd, blk, lds, s, a, ctl, slots, S, G, cs); \
-        else                                                                                       \
-            hipLaunchKernelGGL((k_trace_sched<A, D, T, 0>), grd, blk, lds, s, a, ctl, slots, S, G, cs); \
-    } while (0)
-        TORJ_DISPATCH_TRACE(LAUNCH);
-#undef LAUNCH
-        // the queue's watchdog / retirement state into the sticky flags
-        hipLaunchKernelGGL(k_sched_fold, dim3(1), dim3(1), 0, s, ctl, (unsigned)G, p->d_flags);
-    } else {
-        // small Albajar beams: 16 lanes per ray while n x 16 lanes fit two
-        // waves per SIMD (the latency of a ray's step chain sets the time there)
-        // (TORJ_LPR=1 in the environment turns the automatic choice off)
-        static const int lpr_env = env_int("TORJ_LPR", 0);
-        const bool split = cfg->absorption == 1 && DM != kDepoBinned && p->lanes_per_ray != 1 &&
-                           (p->lanes_per_ray == 16 ||
-                            (lpr_env != 1 && (size_t)n * 16 <= (size_t)p->n_cu * 4 * 2 * 64));
-        const dim3 blk(TORJ_BLOCK);
-        if (split) {
-            const dim3 grd(nblocks(n * 16, TORJ_BLOCK));
-            if (DM == kDepoSamples) {
-                if (tr)
-                    hipLaunchKernelGGL((k_trace<1, kDepoSamples, true, 16>), grd, blk, 0, s, a);
-                else
-                    hipLaunchKernelGGL((k_trace<1, kDepoSamples, false, 16>), grd, blk, 0, s, a);
-            } else {
-                if (tr)
-                    hipLaunchKernelGGL((k_trace<1, kDepoNone, true, 16>), grd, blk, 0, s, a);
-                else
-                    hipLaunchKernelGGL((k_trace<1, kDepoNone, false, 16>), grd, blk, 0, s, a);
-            }
-        } else {
-            const dim3 grd(nblocks(n, TORJ_BLOCK));
-#define LAUNCH(A, D, T) hipLaunchKernelGGL((k_trace<A, D, T>), grd, blk, 0, s, a)
-            TORJ_DISPATCH_TRACE01(LAUNCH);
-#undef LAUNCH
-        }
-    }
-    HIPCK(hipGetLastError());
-    if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
-    if (fit) {
-        if (adaptive)
-            ;  // the last accepted step's FSAL stage already gave P alpha there
-        else if (cfg->absorption == 3)
-            hipLaunchKernelGGL(k_final_alpha<3>, dim3(nblocks(n, 64)), dim3(64), 0, s, a);
-        else if (cfg->absorption == 2)
-            hipLaunchKernelGGL(k_final_alpha<2>, dim3(nblocks(n, 64)), dim3(64), 0, s, a);
-        else if (cfg->absorption == 1)
-            hipLaunchKernelGGL(k_final_alpha<1>, dim3(nblocks(n, 64)), dim3(64), 0, s, a);
-        else
-            hipLaunchKernelGGL(k_final_alpha<0>, dim3(nblocks(n, 64)), dim3(64), 0, s, a);
-        const size_t lds = n_psi <= kFitGridLds ? (size_t)n_psi * sizeof(double) : 0;
-        if (dstr.v)  // the streamed walk's windows ran behind the scans
-            hipLaunchKernelGGL(k_depo_tail, dim3(nblocks(n, 64)), dim3(64), lds, s, fa, dstr);
-        else
-            hipLaunchKernelGGL(k_fit_depo, dim3(nblocks(n, 64)), dim3(64), lds, s, fa);
-        hipLaunchKernelGGL(k_shell_sum, dim3(n_psi), dim3(256), 0, s, fa);
-        HIPCK(hipGetLastError());
-    }
-    if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
-    return 0;
-}
-
-extern "C" {
-
 int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
                          const double *N0, const double *weights, int n_psi, const double *grid,
                          const double *x_launch, const double *s0, double *state, int *status,
@@ -879,54 +557,12 @@ int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, cons
     // contiguous batches of R rays (a multiple of 64), each its own pipeline
     const long sb_rays = (cfg->integrator == 0 && cfg->absorption >= 1) ? env_long("TORJ_SPLIT_BATCH", 0) / 64 * 64 : 0;
     if ((fit || sb_rays > 0) && cfg->n_steps > 0 && x0 && N0 && state && status && steps) {
-        const size_t K = (size_t)cfg->n_steps + 2, L = (size_t)n_psi;
-        const size_t per_ray = fit ? (cfg->integrator == 1 ? 6 : 5) * 8 * K + 4 * (L + 1) + 16 * L + 4 : 0;
+        const size_t per_ray = fit ? fit_bytes_per_ray((size_t)cfg->n_steps + 2, (size_t)n_psi, cfg->integrator == 1) : 0;
         if (ensure_device(p)) return -1;
-        const size_t budget = ws_budget(p);
-        size_t nb_ws = fit && (size_t)n * per_ray > budget ? std::max<size_t>(64, budget / per_ray / 64 * 64) : (size_t)n;
-        if (sb_rays > 0 && (size_t)sb_rays < nb_ws) nb_ws = (size_t)sb_rays;
-        if (nb_ws < (size_t)n) {
-            const int nb = (int)nb_ws;
-            hipStream_t s = (hipStream_t)stream;
-            const int n_save = cfg->traj_stride > 0 && traj ? cfg->n_steps / cfg->traj_stride : 0;
-            const size_t D = sizeof(double), B = (size_t)nb;
-            // staging: x0, N0, x_launch (3 rows), w, s0, P_dep (1), state (7), traj (5 n_save);
-            // status, steps (int)
-            const size_t rows = 3 + 3 + 3 + 1 + 1 + 1 + 7 + 5 * (size_t)n_save;
-            if (ensure_batch(p, rows * B * D + 2 * B * sizeof(int))) return -1;
-            double *q = (double *)p->batch.d;
-            double *bx0 = q, *bN0 = bx0 + 3 * B, *bxl = bN0 + 3 * B, *bw = bxl + 3 * B, *bs0 = bw + B,
-                   *bP = bs0 + B, *bst = bP + B, *btr = bst + 7 * B;
-            int *bstat = (int *)(btr + 5 * (size_t)n_save * B), *bsteps = bstat + B;
-            for (int lo = 0; lo < n; lo += nb) {
-                const int c = std::min(nb, n - lo);
-                auto gather = [&](double *d, const double *h, int r) -> int {
-                    if (!h) return 0;
-                    HIPCK(hipMemcpy2DAsync(d, c * D, h + lo, (size_t)n * D, c * D, r,
-                                           hipMemcpyDeviceToDevice, s));
-                    return 0;
-                };
-                auto scatter = [&](double *h, const double *d, int r) -> int {
-                    if (!h) return 0;
-                    HIPCK(hipMemcpy2DAsync(h + lo, (size_t)n * D, d, c * D, c * D, r,
-                                           hipMemcpyDeviceToDevice, s));
-                    return 0;
-                };
-                if (gather(bx0, x0, 3) || gather(bN0, N0, 3) || gather(bxl, x_launch, 3) ||
-                    gather(bw, weights, 1) || gather(bs0, s0, 1))
-                    return -1;
-                if (trace_device_one(p, cfg, c, bx0, bN0, weights ? bw : nullptr, n_psi, grid,
-                                     x_launch ? bxl : nullptr, s0 ? bs0 : nullptr, bst, bstat, bsteps,
-                                     dP, bP, n_save ? btr : nullptr, counters, stream))
-                    return -1;
-                if (scatter(state, bst, 7) || scatter(Pdep, bP, 1) ||
-                    scatter(n_save ? traj : nullptr, btr, 5 * n_save))
-                    return -1;
-                HIPCK(hipMemcpyAsync(status + lo, bstat, c * sizeof(int), hipMemcpyDeviceToDevice, s));
-                HIPCK(hipMemcpyAsync(steps + lo, bsteps, c * sizeof(int), hipMemcpyDeviceToDevice, s));
-            }
-            return 0;
-        }
+        const size_t nb = batch_rays((size_t)n, per_ray, ws_budget(p), sb_rays);
+        if (nb < (size_t)n)
+            return trace_batched(p, cfg, n, (int)nb, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps,
+                                 dP, Pdep, traj, counters, (hipStream_t)stream);
     }
     return trace_device_one(p, cfg, n, x0, N0, weights, n_psi, grid, x_launch, s0, state, status,
                             steps, dP, Pdep, traj, counters, stream);
@@ -957,48 +593,36 @@ int torj_power_deposition_profile(torj_plasma_t p, int n_rays, const int *n_poin
     }
     if (ensure_device(p)) return -1;
     hipStream_t st = p->stream;
-    const size_t N = (size_t)n_rays, L = (size_t)n_psi, K = (size_t)rows, KN = smp_elems(N, K);
+    const size_t N = (size_t)n_rays, L = (size_t)n_psi;
+    const FitLayout lay = fit_layout(N, (size_t)rows, L, true);  // the trace's workspace, arc lengths stored
     DevBufs B;
-    double *d_s, *d_x, *d_dp, *d_grid, *d_smp, *d_Pr;
-    int *d_np, *d_kstar, *d_cnt;
+    double *d_s, *d_x, *d_dp, *d_grid, *d_Pr;
+    int *d_np;
     long *d_off;
+    char *d_fit;
     if (B.up(&d_s, s, (size_t)tot, st) || B.up(&d_x, x, 3 * (size_t)tot, st) ||
         B.up(&d_dp, dP_ds, (size_t)tot, st) || B.up(&d_grid, grid, L, st) ||
         B.up(&d_np, n_points, N, st) || B.up(&d_off, off.data(), N, st) ||
-        B.alloc(&d_smp, 6 * KN + 2 * L * N, true) || B.alloc(&d_cnt, (L + 1) * N, true) ||
-        B.alloc(&d_kstar, N, true) || B.alloc(&d_Pr, N, true))
+        B.alloc(&d_fit, lay.bytes(), true) || B.alloc(&d_Pr, N, true))
         return -1;
     FitArgs fa{};
+    fit_point(lay, d_fit, fa, nullptr);
     fa.coef = p->d_coef;
     fa.g = p->g;
     fa.n = n_rays;
     fa.n_psi = n_psi;
     fa.grid = d_grid;
-    fa.rows = K;
     fa.npts = d_np;
     fa.steps = d_np;
-    fa.smp_psi = d_smp;
-    fa.smp_dpds = d_smp + KN;
-    fa.smp_s = d_smp + 2 * KN;
-    fa.E = d_smp + 3 * KN;
-    fa.Gpsi = d_smp + 4 * KN;
-    fa.GP = d_smp + 5 * KN;
-    fa.Fopen = d_smp + 6 * KN;
-    fa.dPs = fa.Fopen + L * N;
-    fa.cnt = d_cnt;
-    fa.kstar = d_kstar;
     fa.Pray = d_Pr;
-    HIPCK(hipMemsetAsync(fa.cnt, 0, (L + 1) * N * sizeof(int), st));
-    HIPCK(hipMemsetAsync(fa.Fopen, 0xFF, L * N * sizeof(double), st));  // NaN: every shell closed
-    HIPCK(hipMemsetAsync(fa.dPs, 0, L * N * sizeof(double), st));
+    if (fit_zero(fa, st)) return -1;
     hipLaunchKernelGGL(k_profile_samples, dim3(nblocks(n_rays, 64)), dim3(64), 0, st, fa, d_off, d_s, d_x,
                        (size_t)tot, d_dp);
-    const size_t lds = n_psi <= kFitGridLds ? (size_t)n_psi * sizeof(double) : 0;
-    hipLaunchKernelGGL(k_fit_profile, dim3(nblocks(n_rays, 64)), dim3(64), lds, st, fa);
+    hipLaunchKernelGGL(k_fit_profile, dim3(nblocks(n_rays, 64)), dim3(64), fit_grid_lds(n_psi), st, fa);
     HIPCK(hipGetLastError());
     std::vector<double> dPs(L * N);
     std::vector<int> kstar(N);
-    if (ddownload(dPs.data(), fa.dPs, (L - 1) * N, st) || ddownload(kstar.data(), d_kstar, N, st) ||
+    if (ddownload(dPs.data(), fa.dPs, (L - 1) * N, st) || ddownload(kstar.data(), fa.kstar, N, st) ||
         ddownload(P, d_Pr, N, st))
         return -1;
     HIPCK(hipStreamSynchronize(st));

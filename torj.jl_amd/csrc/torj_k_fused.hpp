@@ -313,7 +313,6 @@ __constant__ double c_ts_bt[7] = {-0.00178001105222577714, -0.000816434459656746
                                   0.007880878010261995,    -0.1447110071732629,
                                   0.5823571654525552,      -0.45808210592918697,
                                   0.015151515151515152};
-constexpr int kTsLds = 7 * 7 * 64;  // doubles per wave
 
 template <int ABS>
 __device__ __forceinline__ void rhs7(const TraceArgs &a, const double u[7], double du[7],

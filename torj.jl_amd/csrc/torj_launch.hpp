@@ -1,0 +1,432 @@
+// torj_launch.hpp -- one launch of the hot path, planned before it is enqueued
+// (the SplitPlan pattern of torj_split.hpp, one level up): launch_plan checks a
+// call's arguments and picks its path from them and the knobs alone (LaunchPlan,
+// no HIP call, no environment read: tests/test_launch_plan.py pins the
+// thresholds on the CPU); fit_layout is the reference deposition's workspace,
+// written once for the trace, torj_power_deposition_profile and the batch size;
+// trace_device_one enqueues what the plan says, one short launcher per path;
+// trace_batched is torj_trace_device_ex's loop over ray batches.  Also here,
+// ahead of its first user: the Gauss-Legendre table's upload.
+// The planning comes first and needs no kernel header: TORJ_LAUNCH_PLAN_ONLY
+// stops there (the CPU test's harness).
+// (a slice of torj_hip.hip: included after `using namespace torj`)
+#pragma once
+#include <algorithm>
+
+#include "../../include/torj_hip.h"
+#include "torj_args.hpp"
+#include "torj_fitdepo.hpp"
+#include "torj_host_util.hpp"
+
+// ---- FitLayout: the reference deposition's workspace.  Samples (psi, dP/ds, and
+// s where the integrator stores it: RK4 has s0 + k ds) and the elimination's
+// coefficients per step, root counts per boundary, open-root integrals and powers
+// per shell, the break shell; in this order ----
+enum FitArr { kFaPsi, kFaDpds, kFaS, kFaE, kFaGpsi, kFaGP, kFaCnt, kFaFopen, kFaDPs, kFaKstar, kFaN };
+
+// array k's bytes per ray
+static size_t fit_arr_bytes(int k, size_t rows, size_t n_psi, bool store_s) {
+    if (k <= kFaGP) return k == kFaS && !store_s ? 0 : sizeof(double) * rows;
+    return k == kFaCnt ? sizeof(int) * (n_psi + 1) : k == kFaKstar ? sizeof(int) : sizeof(double) * n_psi;
+}
+
+// bytes per ray of the layout without its padding: what the batch size is taken from
+static size_t fit_bytes_per_ray(size_t rows, size_t n_psi, bool store_s) {
+    size_t b = 0;
+    for (int k = 0; k < kFaN; k++) b += fit_arr_bytes(k, rows, n_psi, store_s);
+    return b;
+}
+
+struct FitLayout {
+    size_t rows;
+    bool store_s;
+    size_t off[kFaN + 1];  // byte offsets; off[kFaN]: the total
+    size_t bytes() const { return off[kFaN]; }
+};
+
+static FitLayout fit_layout(size_t n, size_t rows, size_t n_psi, bool store_s) {
+    FitLayout l{rows, store_s, {0}};
+    for (int k = 0; k < kFaN; k++) {
+        // per-step arrays hold whole 64-ray blocks (smp_at), the int arrays whole 256 bytes
+        size_t b = fit_arr_bytes(k, rows, n_psi, store_s) * (k <= kFaGP ? smp_elems(n, 1) : n);
+        if (k == kFaCnt || k == kFaKstar) b = (b + 255) & ~(size_t)255;
+        l.off[k + 1] = l.off[k] + b;
+    }
+    return l;
+}
+
+// fa's (and a trace's sample) arrays into the workspace at `base`
+static void fit_point(const FitLayout &l, char *base, FitArgs &fa, TraceArgs *a) {
+    auto D = [&](int k) { return (double *)(base + l.off[k]); };
+    double *const smp_s = l.store_s ? D(kFaS) : nullptr;
+    fa.rows = l.rows;
+    fa.smp_psi = D(kFaPsi), fa.smp_dpds = D(kFaDpds), fa.smp_s = smp_s;
+    fa.E = D(kFaE), fa.Gpsi = D(kFaGpsi), fa.GP = D(kFaGP);
+    fa.Fopen = D(kFaFopen), fa.dPs = D(kFaDPs);
+    fa.cnt = (int *)(base + l.off[kFaCnt]), fa.kstar = (int *)(base + l.off[kFaKstar]);
+    if (a) a->smp_psi = D(kFaPsi), a->smp_dpds = D(kFaDpds), a->smp_s = smp_s, a->smp_rows = l.rows;
+}
+
+// ---- LaunchPlan: what one trace_device_one call launches, fixed before anything is enqueued ----
+// everything the decision reads apart from the call's arguments
+struct LaunchKnobs {
+    int n_cu, sched_mode, sched_waves, lanes_per_ray;  // the handle's (torj_set_sched)
+    // TORJ_SCHED, TORJ_SPLIT, TORJ_SPLIT_WARM (-1 auto, 0 off, 1 on), TORJ_SCHED_W, TORJ_LPR
+    int sched_env, split_env, split_warm_env, w_env, lpr_env;
+};
+// which of the call's pointers are given (rays: x0, N0, state, status and steps, all of them)
+struct LaunchPtrs {
+    bool rays, grid, dP, x_launch, s0, traj;
+};
+enum LaunchPath { kPathSplit, kPathQueue, kPathLane1, kPathLane16 };
+
+struct LaunchPlan {
+    bool depo, fit, tr, adaptive;
+    int DM, n_save;
+    LaunchPath path;
+    int G, cs;  // 64-ray groups; the queue's steps per visit
+    // the queue: W persistent waves, S ring slots, the control block's and the ring's bytes, the
+    // dynamic LDS, and in it the binned shells' per-wave histogram (offset and shells, in doubles)
+    int W;
+    unsigned S;
+    size_t ctl_bytes, lds;
+    int hist_off, n_hist;
+    int grid;       // the one-shot kernels' workgroups
+    FitLayout lay;  // fit only
+};
+
+static int launch_plan(LaunchPlan &pl, const torj_trace_cfg &cfg, int n, int n_psi, const LaunchPtrs &has,
+                       const LaunchKnobs &kn) {
+    if (!has.rays) return fail("x0, N0, state, status, steps required");
+    if (cfg.n_steps < 0) return fail("n_steps < 0");
+    if (cfg.mode != 1 && cfg.mode != -1) return fail("mode must be +1 (X) or -1 (O)");
+    if (!(cfg.ds > 0)) return fail("ds must be > 0");
+    if (cfg.deposition != 0 && cfg.deposition != 1) return fail("deposition must be 0 or 1");
+    if (cfg.integrator != 0 && cfg.integrator != 1) return fail("integrator must be 0 or 1");
+    if (cfg.integrator == 1 && (!(cfg.s_max > 0) || cfg.n_chunks < 1 || !(cfg.abstol > 0) ||
+                                !(cfg.reltol > 0) || cfg.n_steps < 1))
+        return fail("integrator 1 needs s_max > 0, n_chunks >= 1, abstol, reltol > 0, n_steps >= 1");
+    pl = LaunchPlan{};
+    pl.depo = n_psi >= 2 && has.grid && has.dP;
+    pl.fit = pl.depo && cfg.deposition == 1;
+    if (pl.fit && (!has.x_launch || !has.s0))
+        return fail("deposition = 1 (reference profile) needs x_launch and s0 (torj_trace_ex)");
+    if (cfg.absorption < 0 || cfg.absorption > 3) return fail("absorption must be 0..3");
+    pl.tr = cfg.traj_stride > 0 && has.traj;
+    pl.DM = !pl.depo ? kDepoNone : (pl.fit ? kDepoSamples : kDepoBinned);
+    pl.n_save = pl.tr ? cfg.n_steps / cfg.traj_stride : 0;
+    const bool adaptive = pl.adaptive = cfg.integrator == 1, warm = cfg.absorption >= 2;
+    if (pl.fit) pl.lay = fit_layout((size_t)n, (size_t)cfg.n_steps + 2, (size_t)n_psi, adaptive);
+    const int G = pl.G = (n + TORJ_GROUP - 1) / TORJ_GROUP;
+    pl.cs = cfg.chunk_steps > 0 ? cfg.chunk_steps : std::max(cfg.n_steps, 1);
+    // default: the queue pays off once the beam exceeds one wave per SIMD
+    // (measured: 42k rays 111 vs 106 ms one-shot; 100k rays 151 vs 174 ms)
+    const bool big = kn.sched_env && G > kn.n_cu * 4;
+    // the adaptive path runs one tspan chunk per visit and warm always queues; else
+    // any non-zero sched mode is "on": mode 3 sends a cold beam to the queue
+    const bool queue = adaptive || warm || (kn.sched_mode >= 0 ? kn.sched_mode != 0 : big);
+    // the split RK4 path (fixed steps; sched mode 3 forces it):
+    //  * Albajar: by default for beams that would use the work queue;
+    //  * warm weakly relativistic (2): by default -- its alpha kernel runs two
+    //    waves per SIMD where the fused queue kernel holds one (C5: 165 vs 221 ms);
+    //  * warm fully relativistic (3): by default for beams of fewer 64-ray groups
+    //    than 3 per CU, where the one-wave-per-SIMD queue kernel leaves SIMDs idle
+    //    and the split's alpha kernel spreads the points over all of them (129
+    //    rays: 13.1 s -> 0.1 s); on the 1e5-ray fan the queue kernel is faster
+    //    (19.7 vs 20.4 s)
+    const bool albajar_split = cfg.absorption == 1 && kn.split_env == 1 && big;
+    const bool warm_split = warm && kn.split_env == 1 &&
+                            (kn.split_warm_env == 1 ||
+                             (kn.split_warm_env < 0 && (cfg.absorption == 2 || G < kn.n_cu * 3)));
+    // (the split kernels pack a ray's step count into 24 bits beside its status:
+    // 0 < n_steps < kSplitMaxSteps, also under mode 3)
+    const bool split = !adaptive && cfg.absorption >= 1 && cfg.n_steps > 0 && cfg.n_steps < kSplitMaxSteps &&
+                       (kn.sched_mode == 3 || (kn.sched_mode < 0 && (albajar_split || warm_split)));
+    if (split) {
+        pl.path = kPathSplit;
+    } else if (queue && cfg.n_steps > 0) {
+        pl.path = kPathQueue;
+        // W persistent waves: at most 2 per SIMD (4 SIMDs per CU), and fewer
+        // than G so the ready queue keeps a backlog (a wave never waits for a
+        // group while another holds it); TORJ_SCHED_W overrides.
+        const int W = kn.sched_waves > 0 ? kn.sched_waves
+                      : kn.w_env > 0     ? kn.w_env
+                                         : std::min(kn.n_cu * 4 * (warm ? TORJ_WARM_MIN_WAVES : TORJ_MIN_WAVES), G - G / 16);
+        pl.W = std::max(1, std::min(W, G));
+        pl.S = 4u * (unsigned)(G + pl.W);  // ring slots (tag check makes reuse safe)
+        pl.ctl_bytes = 256 + (size_t)pl.S * sizeof(unsigned long long);
+        // binned shells: a per-wave LDS histogram (RK4, up to 4096 shells; the
+        // adaptive path's 25 KB of stage vectors leave no room without losing
+        // occupancy, it keeps the global atomics)
+        pl.hist_off = adaptive ? kTsLds : 0;
+        pl.n_hist = (pl.DM == kDepoBinned && !adaptive && n_psi <= 4096) ? n_psi : 0;
+        pl.lds = (size_t)(pl.hist_off + pl.n_hist) * sizeof(double);
+    } else {
+        // one launch; a beam that would queue comes here with n_steps == 0, the
+        // warm models then on the cold instance (launch_lanes).
+        // Small Albajar beams: 16 lanes per ray while n x 16 lanes fit two
+        // waves per SIMD (the latency of a ray's step chain sets the time there)
+        // (TORJ_LPR=1 in the environment turns the automatic choice off)
+        const bool lanes16 = cfg.absorption == 1 && pl.DM != kDepoBinned && kn.lanes_per_ray != 1 &&
+                             (kn.lanes_per_ray == 16 ||
+                              (kn.lpr_env != 1 && (size_t)n * 16 <= (size_t)kn.n_cu * 4 * 2 * 64));
+        pl.path = lanes16 ? kPathLane16 : kPathLane1;
+        pl.grid = nblocks(lanes16 ? n * 16 : n, TORJ_BLOCK);
+    }
+    return 0;
+}
+
+// rays per launch: all n, or whole 64-ray groups within the workspace budget
+// (per_ray: fit_bytes_per_ray, 0 without the reference deposition), and at most
+// sb_rays when that is set (TORJ_SPLIT_BATCH)
+static size_t batch_rays(size_t n, size_t per_ray, size_t budget, long sb_rays) {
+    const size_t nb = per_ray && n * per_ray > budget ? std::max<size_t>(64, budget / per_ray / 64 * 64) : n;
+    return sb_rays > 0 && (size_t)sb_rays < nb ? (size_t)sb_rays : nb;
+}
+
+#ifndef TORJ_LAUNCH_PLAN_ONLY
+#include <mutex>
+
+#include "torj_dispatch.hpp"
+#include "torj_k_fused.hpp"
+#include "torj_k_points.hpp"
+#include "torj_split.hpp"
+
+// ---- Gauss-Legendre table (abs_Al_init, src/absorption.jl:1-7): the host copy and
+// its upload into c_gl (torj_k_fused.hpp), once per device and version ----
+static std::mutex g_gl_mu;
+static GLTable g_gl_host;
+static int g_gl_version = 0;         // 0: abs_Al_init never called
+static int g_gl_uploaded[64] = {0};  // per device
+
+static int ensure_gl_on_device(int dev) {
+    std::lock_guard<std::mutex> lk(g_gl_mu);
+    if (g_gl_version == 0)
+        return fail(
+            "The weights and abscissae for the absorption were never initialized. Call "
+            "`abs_Al_init` before using the absorption.");
+    if (dev < 0 || dev >= 64) return fail("device index %d out of range", dev);
+    if (g_gl_uploaded[dev] != g_gl_version) {
+        HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(c_gl), &g_gl_host, sizeof(GLTable)));
+        g_gl_uploaded[dev] = g_gl_version;
+    }
+    return 0;
+}
+
+// the knobs of a call on handle p; the environment's are read once, at the first trace
+static LaunchKnobs launch_knobs(const torj_plasma_s *p) {
+    static const int env[5] = {env_int("TORJ_SCHED", 1), env_int("TORJ_SPLIT", 1), env_int("TORJ_SPLIT_WARM", -1),
+                               env_int("TORJ_SCHED_W", 0), env_int("TORJ_LPR", 0)};
+    return {p->n_cu, p->sched_mode, p->sched_waves, p->lanes_per_ray, env[0], env[1], env[2], env[3], env[4]};
+}
+
+// ---- the launchers: one per path, and the phase after the trace ----
+// the work-queue kernel (warm models: the TRAJ instance only, with traj_stride
+// = 0 when no trajectory is wanted -- fewer instances of the heavy warm code)
+static int launch_queue(torj_plasma_s *p, TraceArgs &a, const LaunchPlan &pl, hipStream_t s) {
+    if (ensure_buf(p, p->sched, pl.ctl_bytes)) return -1;
+    HIPCK(hipMemsetAsync(p->sched.d, 0, pl.ctl_bytes, s));
+    SchedCtl *ctl = (SchedCtl *)p->sched.d;
+    unsigned long long *slots = (unsigned long long *)((char *)p->sched.d + 256);
+    const dim3 grd(pl.W), blk(64);
+    a.hist_off = pl.hist_off, a.n_hist = pl.n_hist;
+    with_abs_depo_traj(a.abs_model, pl.DM, pl.tr, [&](auto A, auto D, auto Tr) {
+        constexpr bool T = A() >= 2 || Tr();
+        if (pl.adaptive)
+            hipLaunchKernelGGL((k_trace_sched<A(), D(), T, 1>), grd, blk, pl.lds, s, a, ctl, slots, pl.S, pl.G, pl.cs);
+        else
+            hipLaunchKernelGGL((k_trace_sched<A(), D(), T, 0>), grd, blk, pl.lds, s, a, ctl, slots, pl.S, pl.G, pl.cs);
+    });
+    // the queue's watchdog / retirement state into the sticky flags
+    hipLaunchKernelGGL(k_sched_fold, dim3(1), dim3(1), 0, s, ctl, (unsigned)pl.G, p->d_flags);
+    return 0;
+}
+
+// k_trace, one lane or 16 per ray.  It exists for the cold model and Albajar only
+// (a warm beam gets here with n_steps == 0 alone and takes the cold instance), its
+// 16-lane form for Albajar without binned deposition.
+static void launch_lanes(const TraceArgs &a, const LaunchPlan &pl, hipStream_t s) {
+    const dim3 grd(pl.grid), blk(TORJ_BLOCK);
+    if (pl.path == kPathLane16)
+        with_depo_traj(pl.DM, pl.tr, [&](auto D, auto T) {
+            if constexpr (D() != kDepoBinned) hipLaunchKernelGGL((k_trace<1, D(), T(), 16>), grd, blk, 0, s, a);
+        });
+    else
+        with_abs_depo_traj(a.abs_model == 1 ? 1 : 0, pl.DM, pl.tr, [&](auto A, auto D, auto T) {
+            if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace<A(), D(), T()>), grd, blk, 0, s, a);
+        });
+}
+
+// after a trace with the reference deposition: alpha at the last point, the walk
+// (its tail when the split pipeline streamed it: dstr.v) and the shells' sums
+static int launch_post(const TraceArgs &a, const FitArgs &fa, const LaunchPlan &pl, const DepoStream &dstr,
+                       hipStream_t s) {
+    const dim3 grd(nblocks(a.n, 64)), blk(64);
+    if (!pl.adaptive)  // (adaptive: the last accepted step's FSAL stage already gave P alpha there)
+        with_abs(a.abs_model, [&](auto A) { hipLaunchKernelGGL(k_final_alpha<A()>, grd, blk, 0, s, a); });
+    const size_t lds = fit_grid_lds(fa.n_psi);
+    if (dstr.v)  // the streamed walk's windows ran behind the scans
+        hipLaunchKernelGGL(k_depo_tail, grd, blk, lds, s, fa, dstr);
+    else
+        hipLaunchKernelGGL(k_fit_depo, grd, blk, lds, s, fa);
+    hipLaunchKernelGGL(k_shell_sum, dim3(fa.n_psi), dim3(256), 0, s, fa);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+// torj_timing: this call's three events (start, trace end, post end) from the
+// handle's pool, the first recorded on `s`; all null when timing is off
+static int timing_begin(torj_plasma_s *p, hipEvent_t ev[3], hipStream_t s) {
+    ev[0] = ev[1] = ev[2] = nullptr;
+    if (!p->timing) return 0;
+    while (p->ev_used + 3 > p->ev_pool.size()) {
+        hipEvent_t e;
+        HIPCK(hipEventCreate(&e));
+        p->ev_pool.push_back(e);
+    }
+    for (int q = 0; q < 3; q++) ev[q] = p->ev_pool[p->ev_used + q];
+    p->ev_used += 3;
+    HIPCK(hipEventRecord(ev[0], s));
+    return 0;
+}
+
+// the kernels' arguments that come from the handle, the cfg and the caller's arrays alone
+static TraceArgs trace_args(const torj_plasma_s *p, const torj_trace_cfg &cfg, int n, const double *x0,
+                            const double *N0, const double *weights, const double *s0, double *state,
+                            int *status, int *steps, uint64_t *counters) {
+    TraceArgs a{};
+    a.coef = p->d_coef, a.cellp = p->d_cellp, a.g = p->g;
+    a.k = make_consts(cfg.omega), a.omega = cfg.omega, a.mode = cfg.mode, a.abs_model = cfg.absorption;
+    a.ds = cfg.ds, a.n_steps = cfg.n_steps, a.chunk_steps = cfg.chunk_steps;
+    a.psi_exit = cfg.psi_exit, a.P_min = cfg.P_min;
+    a.n = n, a.x0 = x0, a.N0 = N0, a.w = weights, a.s0 = s0;
+    a.state = state, a.status = status, a.steps = steps, a.counters = (unsigned long long *)counters;
+    if (cfg.integrator == 1) {
+        a.abstol = cfg.abstol, a.reltol = cfg.reltol;
+        a.s_step = cfg.s_max / cfg.n_chunks, a.n_chunks = cfg.n_chunks;
+    }
+    return a;
+}
+
+// the walk's arguments beside its workspace (fit_point), from the trace's
+static void fit_args(FitArgs &fa, const TraceArgs &a, const double *x_launch, bool s_uniform) {
+    fa.coef = a.coef, fa.g = a.g, fa.n = a.n, fa.n_psi = a.n_psi, fa.ds = a.ds;
+    // boundary lookups guess from grid[0], grid[n-1] in-kernel and correct
+    // locally: no host read of the (device-resident) grid, no stream sync
+    fa.grid = a.grid, fa.w = a.w, fa.x_launch = x_launch, fa.s0 = a.s0, fa.steps = a.steps;
+    fa.s_uniform = s_uniform;  // RK4: s_k = s0 + k ds, not stored
+    fa.dP = a.dP, fa.Pray = a.Pdep;
+}
+
+// one launch of the hot path over n rays (the body of torj_trace_device_ex)
+static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
+                            const double *N0, const double *weights, int n_psi, const double *grid,
+                            const double *x_launch, const double *s0, double *state, int *status,
+                            int *steps, double *dP, double *Pdep, double *traj, uint64_t *counters,
+                            void *stream) {
+    if (n <= 0) return 0;
+    const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
+                            x_launch != nullptr, s0 != nullptr, traj != nullptr};
+    LaunchPlan pl;
+    const bool fresh = !p->d_flags;  // n_cu is the device's only once ensure_device has run
+    if (launch_plan(pl, *cfg, n, n_psi, has, launch_knobs(p))) return -1;  // argument errors need no device
+    if (ensure_device(p)) return -1;
+    if (fresh && launch_plan(pl, *cfg, n, n_psi, has, launch_knobs(p))) return -1;
+    if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    TraceArgs a = trace_args(p, *cfg, n, x0, N0, weights, s0, state, status, steps, counters);
+    if (pl.adaptive) {
+        if (ensure_buf(p, p->chunk, (size_t)n * sizeof(int))) return -1;
+        a.chunk = (int *)p->chunk.d;
+    }
+    if (pl.depo) {
+        a.n_psi = n_psi;
+        a.grid = grid;  // uniform-grid fast path is set up in-kernel from grid[0], grid[n-1]
+        a.dP = dP;
+        if (!Pdep) {  // the work-queue kernel carries P_dep across chunks: workspace
+            if (ensure_buf(p, p->ws, (size_t)n * sizeof(double))) return -1;
+            Pdep = (double *)p->ws.d;
+        }
+        a.Pdep = Pdep;
+    }
+    FitArgs fa{};
+    if (pl.fit) {
+        if (ensure_buf(p, p->fit, pl.lay.bytes())) return -1;
+        fit_point(pl.lay, (char *)p->fit.d, fa, &a);
+        fit_args(fa, a, x_launch, !pl.adaptive);
+    }
+    if (pl.depo)  // psi_dP_dV strictly increasing: checked on the device, reported by torj_trace_check
+        hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
+    if (pl.tr) {
+        a.traj_stride = cfg->traj_stride, a.n_save = pl.n_save, a.traj = traj;
+        if (a.n_save > 0)
+            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * n * sizeof(double), s));  // NaN
+    }
+    // the fused / queue paths clear the deposition workspace before the trace
+    // phase's first event (outside trace_ms, as before round 5); the split path
+    // clears it on its scan stream, overlapped with the first trajectory block
+    if (pl.fit && pl.path != kPathSplit && fit_zero(fa, s)) return -1;
+    hipEvent_t ev[3];
+    if (timing_begin(p, ev, s)) return -1;
+    DepoStream dstr{};  // the split pipeline's streamed deposition (split_trace)
+    switch (pl.path) {
+    case kPathSplit:
+        if (split_trace(p, a, pl.DM, pl.tr, s, pl.fit ? &fa : nullptr, &dstr, g_gl_host.negl_skip != 0)) return -1;
+        break;
+    case kPathQueue:
+        if (launch_queue(p, a, pl, s)) return -1;
+        break;
+    case kPathLane1:
+    case kPathLane16: launch_lanes(a, pl, s);
+    }
+    HIPCK(hipGetLastError());
+    if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
+    if (pl.fit && launch_post(a, fa, pl, dstr, s)) return -1;
+    if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
+    return 0;
+}
+
+// ---- ray batches (torj_trace_device_ex): the beam in contiguous batches of nb
+// rays, each its own trace_device_one; the batch's inputs gathered into and its
+// outputs scattered from compact staging ----
+static int trace_batched(torj_plasma_t p, const torj_trace_cfg *cfg, int n, int nb, const double *x0,
+                         const double *N0, const double *weights, int n_psi, const double *grid,
+                         const double *x_launch, const double *s0, double *state, int *status, int *steps,
+                         double *dP, double *Pdep, double *traj, uint64_t *counters, hipStream_t s) {
+    const int n_save = cfg->traj_stride > 0 && traj ? cfg->n_steps / cfg->traj_stride : 0;
+    const size_t D = sizeof(double), B = (size_t)nb;
+    // the staging's double arrays and their rows per ray, in the buffer's order;
+    // status and steps (int) follow them
+    enum { kX0, kN0, kXl, kW, kS0, kP, kSt, kTr, kNb };
+    const int rows[kNb] = {3, 3, 3, 1, 1, 1, 7, 5 * n_save};
+    size_t off[kNb + 1] = {0};  // in rows of B doubles
+    for (int k = 0; k < kNb; k++) off[k + 1] = off[k] + (size_t)rows[k];
+    if (ensure_buf(p, p->batch, off[kNb] * B * D + 2 * B * sizeof(int))) return -1;
+    auto b = [&](int k) { return (double *)p->batch.d + off[k] * B; };
+    int *bstat = (int *)b(kNb), *bsteps = bstat + B;
+    for (int lo = 0; lo < n; lo += nb) {
+        const int c = std::min(nb, n - lo);
+        // array k's rows of c rays from / to the caller's array h (rows of n rays, from ray lo)
+        auto gather = [&](int k, const double *h) -> int {
+            if (!h) return 0;
+            HIPCK(hipMemcpy2DAsync(b(k), c * D, h + lo, (size_t)n * D, c * D, rows[k], hipMemcpyDeviceToDevice, s));
+            return 0;
+        };
+        auto scatter = [&](double *h, int k) -> int {
+            if (!h) return 0;
+            HIPCK(hipMemcpy2DAsync(h + lo, (size_t)n * D, b(k), c * D, c * D, rows[k], hipMemcpyDeviceToDevice, s));
+            return 0;
+        };
+        if (gather(kX0, x0) || gather(kN0, N0) || gather(kXl, x_launch) || gather(kW, weights) || gather(kS0, s0))
+            return -1;
+        if (trace_device_one(p, cfg, c, b(kX0), b(kN0), weights ? b(kW) : nullptr, n_psi, grid,
+                             x_launch ? b(kXl) : nullptr, s0 ? b(kS0) : nullptr, b(kSt), bstat, bsteps, dP, b(kP),
+                             n_save ? b(kTr) : nullptr, counters, s))
+            return -1;
+        if (scatter(state, kSt) || scatter(Pdep, kP) || scatter(n_save ? traj : nullptr, kTr)) return -1;
+        HIPCK(hipMemcpyAsync(status + lo, bstat, c * sizeof(int), hipMemcpyDeviceToDevice, s));
+        HIPCK(hipMemcpyAsync(steps + lo, bsteps, c * sizeof(int), hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+#endif  // TORJ_LAUNCH_PLAN_ONLY

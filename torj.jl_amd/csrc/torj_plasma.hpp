@@ -240,19 +240,10 @@ static int ensure_device(torj_plasma_s *p) {
     return 0;
 }
 
-static int ensure_sched(torj_plasma_s *p, size_t bytes) {
+// one of the handle's grow-only buffers at `bytes` or more, under the handle's lock
+static int ensure_buf(torj_plasma_s *p, GrowBuf &b, size_t bytes) {
     std::lock_guard<std::mutex> lk(p->mu);
-    return p->sched.reserve(bytes);
-}
-
-static int ensure_chunks(torj_plasma_s *p, size_t n) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    return p->chunk.reserve(n * sizeof(int));
-}
-
-static int ensure_fit(torj_plasma_s *p, size_t bytes) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    return p->fit.reserve(bytes);
+    return b.reserve(bytes);
 }
 
 // a split-pipeline stream's priority: `dflt`, or the environment's value clamped
@@ -268,6 +259,14 @@ static int stream_prio(const char *name, int dflt, int lo, int hi) {
     const int v = std::min(std::max(env_int(name, dflt), std::min(lo, hi)), std::max(lo, hi));
     if (verbose) fprintf(stderr, "torj: %s -> %d\n", name, v);
     return v;
+}
+
+// a CU mask of k of the device's ncu CUs, spread evenly over its bits (rest: the others)
+static std::vector<uint32_t> cu_mask(int ncu, int k, bool rest = false) {
+    std::vector<uint32_t> m((ncu + 31) / 32, 0u);
+    for (int c = 0; c < ncu; c++)
+        if ((((long)(c + 1) * k) / ncu != ((long)c * k) / ncu) != rest) m[c / 32] |= 1u << (c % 32);
+    return m;
 }
 
 static int ensure_split(torj_plasma_s *p, size_t bytes) {
@@ -286,18 +285,12 @@ static int ensure_split(torj_plasma_s *p, size_t bytes) {
         if (Y > 0 && Y < ncu) {
             // TORJ_ALPHA_CUS=Y: only the alpha and scan streams masked (to Y CUs),
             // the trajectory stream on every CU -- the others never hold alpha waves
-            std::vector<uint32_t> mA((ncu + 31) / 32, 0u);
-            for (int c = 0; c < ncu; c++)
-                if (((long)(c + 1) * Y) / ncu != ((long)c * Y) / ncu) mA[c / 32] |= 1u << (c % 32);
+            const std::vector<uint32_t> mA = cu_mask(ncu, Y);
             HIPCK(hipStreamCreateWithPriority(&p->streamT, hipStreamNonBlocking, hi));
             HIPCK(hipExtStreamCreateWithCUMask(&p->stream2, (uint32_t)mA.size(), mA.data()));
             HIPCK(hipExtStreamCreateWithCUMask(&p->streamS, (uint32_t)mA.size(), mA.data()));
         } else if (X > 0 && X < ncu) {
-            std::vector<uint32_t> mT((ncu + 31) / 32, 0u), mA((ncu + 31) / 32, 0u);
-            for (int c = 0; c < ncu; c++) {
-                const bool t = ((long)(c + 1) * X) / ncu != ((long)c * X) / ncu;
-                (t ? mT : mA)[c / 32] |= 1u << (c % 32);
-            }
+            const std::vector<uint32_t> mT = cu_mask(ncu, X), mA = cu_mask(ncu, X, true);
             HIPCK(hipExtStreamCreateWithCUMask(&p->streamT, (uint32_t)mT.size(), mT.data()));
             HIPCK(hipExtStreamCreateWithCUMask(&p->stream2, (uint32_t)mA.size(), mA.data()));
             HIPCK(hipExtStreamCreateWithCUMask(&p->streamS, (uint32_t)mA.size(), mA.data()));
@@ -310,9 +303,7 @@ static int ensure_split(torj_plasma_s *p, size_t bytes) {
             // keep their registers for the alpha waves
             const int Z = env_int("TORJ_SCAN_CUS", 0);
             if (Z > 0 && Z < ncu) {
-                std::vector<uint32_t> mS((ncu + 31) / 32, 0u);
-                for (int c = 0; c < ncu; c++)
-                    if (((long)(c + 1) * Z) / ncu != ((long)c * Z) / ncu) mS[c / 32] |= 1u << (c % 32);
+                const std::vector<uint32_t> mS = cu_mask(ncu, Z);
                 HIPCK(hipExtStreamCreateWithCUMask(&p->streamS, (uint32_t)mS.size(), mS.data()));
             } else {
                 HIPCK(hipStreamCreateWithPriority(&p->streamS, hipStreamNonBlocking, stream_prio("TORJ_SCAN_PRIO", lo, lo, hi)));
@@ -328,11 +319,6 @@ static int ensure_split(torj_plasma_s *p, size_t bytes) {
         HIPCK(hipEventCreateWithFlags(&p->ev_D, hipEventDisableTiming));
     }
     return p->split.reserve(bytes);
-}
-
-static int ensure_workspace(torj_plasma_s *p, size_t n) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    return p->ws.reserve(n * sizeof(double));
 }
 
 // Device-memory budget of one launch's per-ray workspace (the reference
@@ -353,10 +339,5 @@ static size_t ws_budget(const torj_plasma_s *p) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return floor16;
     return std::max(floor16, (free_b + p->fit.cap) / 2);
-}
-
-static int ensure_batch(torj_plasma_s *p, size_t bytes) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    return p->batch.reserve(bytes);
 }
 

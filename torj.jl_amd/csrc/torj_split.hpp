@@ -5,11 +5,15 @@
 #pragma once
 #include <atomic>
 
+#include "torj_dispatch.hpp"
 #include "torj_k_alpha.hpp"
 #include "torj_k_depo.hpp"
 #include "torj_k_scan.hpp"
 #include "torj_k_traj.hpp"
 #include "torj_plasma.hpp"
+
+// dynamic LDS of the walk kernels: the shell grid, when it fits
+static size_t fit_grid_lds(int n_psi) { return n_psi <= kFitGridLds ? (size_t)n_psi * sizeof(double) : 0; }
 
 // the reference deposition walk's per-boundary root counts, open-shell spill
 // (NaN: every shell closed) and per-ray shell powers, cleared before the walk
@@ -250,7 +254,7 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
     // there), so the clearing overlaps the first trajectory block instead of
     // delaying it (0.5 ms per headline launch)
     if (fa && fit_zero(*fa, s3)) return -1;
-    const size_t fit_lds = fa && fa->n_psi <= kFitGridLds ? (size_t)fa->n_psi * sizeof(double) : 0;
+    const size_t fit_lds = fa ? fit_grid_lds(fa->n_psi) : 0;
     const int G = (int)((n + 63) / 64);
     const size_t lds_bytes = (size_t)(a.g.nR + 2) * (a.g.nZ + 2) * kTrajLdsNS * sizeof(double);
     const bool lds_traj = pl.lds_env == 1 && lds_bytes <= 160 * 1024;
@@ -264,19 +268,6 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
         hipLaunchKernelGGL(k_depo_elim, dim3(G), dim3(64), 0, st, *fa, ds, sp.sinfo, cap);
         hipLaunchKernelGGL(k_depo_walk, dim3(G), dim3(64), fit_lds, st, *fa, ds, sp.sinfo, cap);
     };
-#define TORJ_SPLIT_DISPATCH(K, ...)                                                         \
-    do {                                                                                    \
-        if (DM == kDepoSamples) {                                                           \
-            if (tr) hipLaunchKernelGGL((K<kDepoSamples, true>), __VA_ARGS__);               \
-            else hipLaunchKernelGGL((K<kDepoSamples, false>), __VA_ARGS__);                 \
-        } else if (DM == kDepoBinned) {                                                     \
-            if (tr) hipLaunchKernelGGL((K<kDepoBinned, true>), __VA_ARGS__);                \
-            else hipLaunchKernelGGL((K<kDepoBinned, false>), __VA_ARGS__);                  \
-        } else {                                                                            \
-            if (tr) hipLaunchKernelGGL((K<kDepoNone, true>), __VA_ARGS__);                  \
-            else hipLaunchKernelGGL((K<kDepoNone, false>), __VA_ARGS__);                    \
-        }                                                                                   \
-    } while (0)
     for (int b = 0; b < n_blocks; b++) {
         sp.k0 = pl.block_k0(b);
         sp.kb = pl.block_len(b);
@@ -294,14 +285,16 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
             HIPCK(hipStreamWaitEvent(sT, p->ev_S[bw % R], 0));
             depo_pair(sT, pl.window_cap(bw));
         }
-        if (cell_traj)
-            TORJ_SPLIT_DISPATCH(k_traj_cell, dim3(G), dim3(64), 0, sT, a, sp);
-        else if (tile_traj)
-            TORJ_SPLIT_DISPATCH(k_traj_tile, dim3(G), dim3(64), 0, sT, a, sp);
-        else if (lds_traj)
-            TORJ_SPLIT_DISPATCH(k_traj_lds, dim3(nblocks(G, wpb)), dim3(64 * wpb), lds_bytes, sT, a, sp);
-        else
-            TORJ_SPLIT_DISPATCH(k_traj, dim3(G), dim3(64), 0, sT, a, sp);
+        with_depo_traj(DM, tr, [&](auto D, auto T) {
+            if (cell_traj)
+                hipLaunchKernelGGL((k_traj_cell<D(), T()>), dim3(G), dim3(64), 0, sT, a, sp);
+            else if (tile_traj)
+                hipLaunchKernelGGL((k_traj_tile<D(), T()>), dim3(G), dim3(64), 0, sT, a, sp);
+            else if (lds_traj)
+                hipLaunchKernelGGL((k_traj_lds<D(), T()>), dim3(nblocks(G, wpb)), dim3(64 * wpb), lds_bytes, sT, a, sp);
+            else
+                hipLaunchKernelGGL((k_traj<D(), T()>), dim3(G), dim3(64), 0, sT, a, sp);
+        });
         HIPCK(hipEventRecord(p->ev_T[r], sT));
         HIPCK(hipStreamWaitEvent(s2, p->ev_T[r], 0));
         const int nqA = (int)((n + kAlphaBlock - 1) / kAlphaBlock);
@@ -338,10 +331,12 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
 #endif
         HIPCK(hipEventRecord(p->ev_A[r], s2));
         if (s3 != s2) HIPCK(hipStreamWaitEvent(s3, p->ev_A[r], 0));
-        if (a.counters)
-            TORJ_SPLIT_DISPATCH(k_tau_scan_counted, dim3(G), dim3(64), 0, s3, a, sp);
-        else
-            TORJ_SPLIT_DISPATCH(k_tau_scan, dim3(G), dim3(64), 0, s3, a, sp);
+        with_depo_traj(DM, tr, [&](auto D, auto T) {
+            if (a.counters)
+                hipLaunchKernelGGL((k_tau_scan_counted<D(), T()>), dim3(G), dim3(64), 0, s3, a, sp);
+            else
+                hipLaunchKernelGGL((k_tau_scan<D(), T()>), dim3(G), dim3(64), 0, s3, a, sp);
+        });
         HIPCK(hipEventRecord(p->ev_S[r], s3));
         // the deposition walk's windows behind this scan (same stream: after it,
         // and the next scan after them; the ring slot is already released)
@@ -368,8 +363,9 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
             depo_pair(sT, pl.window_cap(bw));
         }
     }
-    TORJ_SPLIT_DISPATCH(k_split_final, dim3(G), dim3(64), 0, s3, a, sp);
-#undef TORJ_SPLIT_DISPATCH
+    with_depo_traj(DM, tr, [&](auto D, auto T) {
+        hipLaunchKernelGGL((k_split_final<D(), T()>), dim3(G), dim3(64), 0, s3, a, sp);
+    });
     if (!serial) {  // join: the final kernel followed every scan, each scan its alpha kernel
                     // and each alpha kernel its trajectory
         HIPCK(hipEventRecord(p->ev_J, s3));
