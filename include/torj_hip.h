@@ -37,7 +37,9 @@ extern "C" {
 #define TORJ_ABI_VERSION 8  /* 3: torj_trace_beam, sticky launch flags; 4: 8 work counters;
                                5: torj_trace_beam_device, torj_power_deposition_profile;
                                6: torj_beam_timing_read, torj_trace_beam's automatic shards;
-                               7: torj_build_id; 8: torj_beam_comm_info */
+                               7: torj_build_id; 8: torj_beam_comm_info; still 8 (symbols added,
+                               nothing changed): torj_trace_beams, torj_trace_beams_device,
+                               torj_ray_entry_beams_gpu, torj_ray_entry_beams_device */
 
 /* per-ray status codes (replace the reference's @assert / unhandled returns) */
 enum torj_status {
@@ -242,6 +244,55 @@ int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, cons
                          const double *psi_grid, const double *x_launch, const double *s0,
                          double *state, int *status, int *steps, double *dP_shell, double *P_dep,
                          double *traj, uint64_t *counters, void *stream);
+
+/* ---- many small beams of differing frequency and mode in one launch -------
+ * (no reference counterpart: an EC system of tens of launchers is tens of
+ * make_beam calls there, src/solve.jl:209-242).  The rays of n_beams beams are
+ * concatenated: beam b owns rays beam_off[b] .. beam_off[b+1] - 1 of every
+ * per-ray array (beam_off[0] = 0, non-decreasing, empty beams allowed; the
+ * arrays hold n = beam_off[n_beams] rays), is traced with omega[b] and mode[b]
+ * (cfg->omega and cfg->mode are ignored; every other cfg field is shared) and
+ * deposits into row b of dP_shell, n_beams rows of n_psi + 1 laid out as
+ * torj_trace's one.  n_beams <= 4096.  One launch of the one-shot kernel whatever
+ * the size (torj_set_sched modes 1 and 3 are refused), with absorption 0 or 1
+ * and integrator 0 only.  Lanes per ray as for a single beam (16 for Albajar
+ * without binned deposition while the launch's waves fit two per SIMD;
+ * torj_set_sched 0 / 2 and env TORJ_LPR=1 force it).  No wave of the launch
+ * mixes beams and a beam's waves hold the rays they would hold were the beam
+ * traced alone, so every per-ray output, and with deposition = 1 every dP_shell
+ * row, equals bit for bit what torj_trace_device_ex gives for that beam with
+ * the same lanes per ray (binned rows: up to the order of the atomic sums).
+ * With deposition = 1 the workspace holds all n rays at once: a launch beyond
+ * the budget (TORJ_WS_GB) is an error, not batched -- trace such beams in
+ * separate calls.
+ * beam_off, omega and mode are HOST arrays in both forms (n_beams + 1, n_beams,
+ * n_beams) and are consumed before the call returns: the caller may overwrite
+ * them at once, also between two calls enqueued on one stream.
+ * _device: every other pointer is device memory, enqueued on `stream` as
+ * torj_trace_device_ex is (NULL stream, torj_timing, torj_trace_check's sticky
+ * flags, one stream per handle); dP_shell is accumulated into; counters are sums
+ * over all beams.  torj_trace_beams: host pointers, synchronous, checked. */
+int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams,
+                            const int *beam_off, const double *omega, const int *mode,
+                            const double *x0, const double *N0, const double *weights, int n_psi,
+                            const double *psi_grid, const double *x_launch, const double *s0,
+                            double *state, int *status, int *steps, double *dP_shell,
+                            double *P_dep, double *traj, uint64_t *counters, void *stream);
+int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+                     const double *omega, const int *mode, const double *x0, const double *N0,
+                     const double *weights, int n_psi, const double *psi_grid,
+                     const double *x_launch, const double *s0, double *state, int *status,
+                     int *steps, double *dP_shell, double *P_dep, double *traj);
+/* torj_ray_entry_device / _gpu for the same concatenated beams: ray i enters
+ * with its beam's omega and mode (host tables as above). */
+int torj_ray_entry_beams_device(torj_plasma_t p, int n_beams, const int *beam_off,
+                                const double *omega, const int *mode, const double *x0,
+                                const double *N0, double *x_plasma, double *N_plasma, double *s0,
+                                int *status, void *stream);
+int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off,
+                             const double *omega, const int *mode, const double *x0,
+                             const double *N0, double *x_plasma, double *N_plasma, double *s0,
+                             int *status);
 
 /* make_beam's fan-out and reduce across the GPUs of this process
  * (src/solve.jl:209-240: one task per ray, then sum_i w_i dP_dV_i and

@@ -142,3 +142,24 @@ constexpr int kTileCells = TORJ_TILE_CELLS;
 #ifndef TORJ_TRAJ_TILE_WAVES
 #define TORJ_TRAJ_TILE_WAVES 2
 #endif
+
+// ---- a multi-beam launch (torj_k_beams.hpp; planned by torj_launch.hpp beams_plan) ----
+// beam b: rays lo .. hi - 1 of the concatenated arrays, its own frequency and mode
+struct BeamRec {
+    double omega;
+    Consts k;
+    int mode;
+    int lo, hi;
+};
+// wave w of the launch: its beam and the first ray it carries (a wave never mixes beams)
+struct BeamWave {
+    int beam, first;
+};
+// the trace's arguments (omega, k, mode unused: the wave's beam gives them; dP: row 0
+// of n_beams rows of n_psi + 1) and the two tables, device-resident
+struct BeamsArgs {
+    TraceArgs a;
+    const BeamRec *beams;
+    const BeamWave *waves;
+    int n_beams;
+};

@@ -8,6 +8,7 @@
 //   torj_k_scan.hpp     ... its optical-depth scan and final assembly
 //   torj_k_depo.hpp     the reference-faithful deposition's kernels
 //   torj_k_points.hpp   ray entry and the batched point evaluations
+//   torj_k_beams.hpp    the multi-beam forms of k_trace and the kernels around it
 //   torj_host_util.hpp  fail / HIPCK, the environment knobs, GrowBuf
 //   torj_plasma.hpp     the plasma handle and its device state
 //   torj_fan.hpp        quadrature nodes and the launch fan
@@ -43,6 +44,7 @@ using namespace torj;
 #include "torj_k_scan.hpp"
 #include "torj_k_depo.hpp"
 #include "torj_k_points.hpp"
+#include "torj_k_beams.hpp"
 #include "torj_plasma.hpp"
 #include "torj_fan.hpp"
 #include "torj_split.hpp"
@@ -222,6 +224,7 @@ int torj_plasma_destroy(torj_plasma_t p) {
     if (p->chunk.d) (void)hipFree(p->chunk.d);
     for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
     if (p->ws.d) (void)hipFree(p->ws.d);
+    if (p->beams.d) (void)hipFree(p->beams.d);
     if (p->split.d) (void)hipFree(p->split.d);
     if (p->batch.d) (void)hipFree(p->batch.d);
     for (int q = 0; q < torj_plasma_s::kRing; q++) {
@@ -566,6 +569,135 @@ int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, cons
     }
     return trace_device_one(p, cfg, n, x0, N0, weights, n_psi, grid, x_launch, s0, state, status,
                             steps, dP, Pdep, traj, counters, stream);
+}
+
+// ---- many beams of differing frequency and mode in one launch (beams_plan, torj_k_beams.hpp) ----
+int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+                            const double *omega, const int *mode, const double *x0, const double *N0,
+                            const double *weights, int n_psi, const double *grid, const double *x_launch,
+                            const double *s0, double *state, int *status, int *steps, double *dP,
+                            double *Pdep, double *traj, uint64_t *counters, void *stream) {
+    if (!p || !cfg) return fail("bad plasma handle or cfg");
+    if (!stream) {  // the NULL stream as the caller's: torj_trace_device_ex's fork and join
+        // (argument errors first, without a device)
+        BeamsPlan bp;
+        const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
+                                x_launch != nullptr, s0 != nullptr, traj != nullptr};
+        if (beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+        if (ensure_device(p)) return -1;
+        if (!p->ev_Nin) {
+            HIPCK(hipEventCreateWithFlags(&p->ev_Nin, hipEventDisableTiming));
+            HIPCK(hipEventCreateWithFlags(&p->ev_Nout, hipEventDisableTiming));
+        }
+        HIPCK(hipEventRecord(p->ev_Nin, nullptr));
+        HIPCK(hipStreamWaitEvent(p->stream, p->ev_Nin, 0));
+        const int rc = torj_trace_beams_device(p, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid,
+                                               x_launch, s0, state, status, steps, dP, Pdep, traj, counters, p->stream);
+        HIPCK(hipEventRecord(p->ev_Nout, p->stream));
+        HIPCK(hipStreamWaitEvent(nullptr, p->ev_Nout, 0));
+        return rc;
+    }
+    if (p->timing) p->timing_calls++;
+    return beams_trace_device(p, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
+                              state, status, steps, dP, Pdep, traj, counters, (hipStream_t)stream);
+}
+
+int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+                     const double *omega, const int *mode, const double *x0, const double *N0,
+                     const double *weights, int n_psi, const double *grid, const double *x_launch,
+                     const double *s0, double *state, int *status, int *steps, double *dP, double *Pdep,
+                     double *traj) {
+    if (!p || !cfg) return fail("bad plasma handle or cfg");
+    const bool depo = n_psi >= 2 && grid;
+    {  // argument errors before any device work (the device form repeats them on its pointers)
+        BeamsPlan bp;
+        const LaunchPtrs has = {x0 && N0 && state && status && steps, depo, depo, x_launch != nullptr,
+                                s0 != nullptr, traj != nullptr};
+        if (beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+    }
+    if (depo)
+        for (int k = 1; k < n_psi; k++)
+            if (!(grid[k] > grid[k - 1])) return fail("psi_dP_dV must be strictly increasing");
+    const int n = beam_off[n_beams];
+    const size_t rows = (size_t)n_beams * (size_t)(n_psi > 0 ? n_psi + 1 : 1);
+    if (n == 0) {
+        if (dP) std::fill(dP, dP + rows, 0.0);
+        return 0;
+    }
+    if (ensure_device(p)) return -1;
+    hipStream_t s = p->stream;
+    const int n_save = cfg->traj_stride > 0 ? cfg->n_steps / cfg->traj_stride : 0;
+    DevBufs B;
+    double *dx0, *dN0, *dw = nullptr, *dgrid = nullptr, *dstate, *ddP = nullptr, *dPdep = nullptr, *dtraj = nullptr,
+                       *dxl = nullptr, *ds0 = nullptr;
+    int *dstatus, *dsteps;
+    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s) || B.up(&dw, weights, n, s) ||
+        B.up(&dxl, x_launch, 3 * (size_t)n, s) || B.up(&ds0, s0, n, s))
+        return -1;
+    if (depo) {
+        if (B.up(&dgrid, grid, n_psi, s) || B.alloc(&ddP, rows, true) || B.alloc(&dPdep, n, true)) return -1;
+        HIPCK(hipMemsetAsync(ddP, 0, rows * sizeof(double), s));
+    }
+    if (B.alloc(&dstate, 7 * (size_t)n, true) || B.alloc(&dstatus, n, true) || B.alloc(&dsteps, n, true) ||
+        B.alloc(&dtraj, (size_t)n_save * 5 * n, traj && n_save > 0))
+        return -1;
+    if (torj_trace_beams_device(p, cfg, n_beams, beam_off, omega, mode, dx0, dN0, dw, depo ? n_psi : 0, dgrid, dxl,
+                                ds0, dstate, dstatus, dsteps, ddP, dPdep, dtraj, nullptr, s))
+        return -1;
+    if (ddownload(state, dstate, 7 * (size_t)n, s) || ddownload(status, dstatus, n, s) ||
+        ddownload(steps, dsteps, n, s))
+        return -1;
+    if (depo) {
+        if (ddownload(dP, ddP, rows, s) || ddownload(Pdep, dPdep, n, s)) return -1;
+    } else {
+        if (dP) std::fill(dP, dP + rows, 0.0);
+        if (Pdep) std::fill(Pdep, Pdep + n, 0.0);
+    }
+    if (traj && n_save > 0 && ddownload(traj, dtraj, (size_t)n_save * 5 * n, s)) return -1;
+    return torj_trace_check(p, s);
+}
+
+int torj_ray_entry_beams_device(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
+                                const int *mode, const double *x0, const double *N0, double *xp, double *Np,
+                                double *s0, int *status, void *stream) {
+    if (!p) return fail("bad plasma handle");
+    if (beams_tables_check(n_beams, beam_off, omega, mode)) return -1;
+    if (!x0 || !N0 || !xp || !Np || !s0 || !status) return fail("x0, N0, x_plasma, N_plasma, s0, status required");
+    const int n = beam_off[n_beams];
+    if (n == 0) return 0;
+    if (ensure_device(p)) return -1;
+    const BeamRec *d_beams;
+    if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, (hipStream_t)stream, &d_beams, nullptr))
+        return -1;
+    EntryArgs a{p->d_coef, p->g, p->psi_prof_max, 0.0, 0, n, x0, N0, xp, Np, s0, status};
+    hipLaunchKernelGGL(k_ray_entry_beams, dim3(nblocks(n, 64)), dim3(64), 0, (hipStream_t)stream, a, d_beams, n_beams);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
+                             const int *mode, const double *x0, const double *N0, double *xp, double *Np,
+                             double *s0, int *status) {
+    if (!p) return fail("bad plasma handle");
+    if (beams_tables_check(n_beams, beam_off, omega, mode)) return -1;
+    if (!x0 || !N0 || !xp || !Np || !s0 || !status) return fail("x0, N0, x_plasma, N_plasma, s0, status required");
+    const int n = beam_off[n_beams];
+    if (n == 0) return 0;
+    if (ensure_device(p)) return -1;
+    hipStream_t s = p->stream;
+    DevBufs B;
+    double *dx0, *dN0, *dxp, *dNp, *ds0;
+    int *dst;
+    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s)) return -1;
+    if (B.alloc(&dxp, 3 * (size_t)n, true) || B.alloc(&dNp, 3 * (size_t)n, true) || B.alloc(&ds0, n, true) ||
+        B.alloc(&dst, n, true))
+        return -1;
+    if (torj_ray_entry_beams_device(p, n_beams, beam_off, omega, mode, dx0, dN0, dxp, dNp, ds0, dst, s)) return -1;
+    if (ddownload(xp, dxp, 3 * (size_t)n, s) || ddownload(Np, dNp, 3 * (size_t)n, s) || ddownload(s0, ds0, n, s) ||
+        ddownload(status, dst, n, s))
+        return -1;
+    HIPCK(hipStreamSynchronize(s));
+    return 0;
 }
 
 int torj_power_deposition_profile(torj_plasma_t p, int n_rays, const int *n_points, const double *s,

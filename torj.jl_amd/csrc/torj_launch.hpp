@@ -5,13 +5,16 @@
 // thresholds on the CPU); fit_layout is the reference deposition's workspace,
 // written once for the trace, torj_power_deposition_profile and the batch size;
 // trace_device_one enqueues what the plan says, one short launcher per path;
-// trace_batched is torj_trace_device_ex's loop over ray batches.  Also here,
+// trace_batched is torj_trace_device_ex's loop over ray batches; beams_plan and
+// beams_trace_device are the same two steps for a multi-beam launch.  Also here,
 // ahead of its first user: the Gauss-Legendre table's upload.
 // The planning comes first and needs no kernel header: TORJ_LAUNCH_PLAN_ONLY
 // stops there (the CPU test's harness).
 // (a slice of torj_hip.hip: included after `using namespace torj`)
 #pragma once
 #include <algorithm>
+#include <cmath>
+#include <vector>
 
 #include "../../include/torj_hip.h"
 #include "torj_args.hpp"
@@ -184,10 +187,92 @@ static size_t batch_rays(size_t n, size_t per_ray, size_t budget, long sb_rays) 
     return sb_rays > 0 && (size_t)sb_rays < nb ? (size_t)sb_rays : nb;
 }
 
+// ---- BeamsPlan: a multi-beam launch of the one-shot kernel (torj_trace_beams_device):
+// B beams' rays concatenated, beam b rays beam_off[b] .. beam_off[b + 1] - 1 with its
+// own omega[b] and mode[b] (cfg.omega, cfg.mode unused) and row b of dP_shell.
+// The wave table: beam b takes ceil(n_b / (64 / LPR)) waves, wave j of a beam its rays
+// (64 / LPR) j ..., exactly k_trace's lanes on that beam alone -- a wave never mixes
+// beams, so the 16-lane Albajar code's per-wave choices see the rays they would in a
+// single-beam launch (bit-identical results) and the beam's constants are wave-uniform.
+// At most kMaxBeams beams: k_shell_sum_beams' grid is (n_psi, n_beams), its y extent
+// limited to 65 535.
+constexpr int kMaxBeams = 4096;
+
+struct BeamsPlan {
+    bool depo, fit, tr;
+    int DM, n_save;
+    int n;    // rays of all beams
+    int lpr;  // lanes per ray: 1 or 16
+    FitLayout lay;  // fit only, for all n rays
+    std::vector<BeamRec> beams;
+    std::vector<BeamWave> waves;  // the launch's workgroups, one wave each
+};
+
+// the three host tables of a multi-beam call, checked (the trace's and the ray entry's)
+static int beams_tables_check(int n_beams, const int *beam_off, const double *omega, const int *mode) {
+    if (n_beams < 1 || n_beams > kMaxBeams) return fail("n_beams must be 1..%d", kMaxBeams);
+    if (!beam_off) return fail("beam_off is NULL");
+    if (!omega || !mode) return fail("omega and mode (n_beams each) required");
+    if (beam_off[0] != 0) return fail("beam_off[0] must be 0");
+    for (int b = 0; b < n_beams; b++)
+        if (beam_off[b + 1] < beam_off[b]) return fail("beam_off must not decrease (beam %d)", b);
+    for (int b = 0; b < n_beams; b++) {
+        if (!(omega[b] > 0) || !std::isfinite(omega[b])) return fail("omega[%d] must be finite and > 0", b);
+        if (mode[b] != 1 && mode[b] != -1) return fail("mode[%d] must be +1 (X) or -1 (O)", b);
+    }
+    return 0;
+}
+static std::vector<BeamRec> beams_records(int n_beams, const int *beam_off, const double *omega, const int *mode) {
+    std::vector<BeamRec> r(n_beams);
+    for (int b = 0; b < n_beams; b++)
+        r[b] = BeamRec{omega[b], make_consts(omega[b]), mode[b], beam_off[b], beam_off[b + 1]};
+    return r;
+}
+
+static int beams_plan(BeamsPlan &bp, const torj_trace_cfg &cfg, int n_beams, const int *beam_off,
+                      const double *omega, const int *mode, int n_psi, const LaunchPtrs &has,
+                      const LaunchKnobs &kn) {
+    if (beams_tables_check(n_beams, beam_off, omega, mode)) return -1;
+    if (!has.rays) return fail("x0, N0, state, status, steps required");
+    if (cfg.n_steps < 0) return fail("n_steps < 0");
+    if (!(cfg.ds > 0)) return fail("ds must be > 0");
+    if (cfg.deposition != 0 && cfg.deposition != 1) return fail("deposition must be 0 or 1");
+    if (cfg.absorption != 0 && cfg.absorption != 1)
+        return fail("absorption must be 0 or 1 in a multi-beam launch (the warm models trace one beam per call)");
+    if (cfg.integrator != 0)
+        return fail("integrator must be 0 in a multi-beam launch (the adaptive integrator traces one beam per call)");
+    if (kn.sched_mode == 1 || kn.sched_mode == 3)
+        return fail("sched mode %d has no multi-beam form: only the one-shot kernel (torj_set_sched -1, 0, 2)",
+                    kn.sched_mode);
+    bp = BeamsPlan{};
+    bp.depo = n_psi >= 2 && has.grid && has.dP;
+    bp.fit = bp.depo && cfg.deposition == 1;
+    if (bp.fit && (!has.x_launch || !has.s0))
+        return fail("deposition = 1 (reference profile) needs x_launch and s0 (torj_trace_ex)");
+    bp.tr = cfg.traj_stride > 0 && has.traj;
+    bp.DM = !bp.depo ? kDepoNone : (bp.fit ? kDepoSamples : kDepoBinned);
+    bp.n_save = bp.tr ? cfg.n_steps / cfg.traj_stride : 0;
+    bp.n = beam_off[n_beams];
+    if (bp.fit) bp.lay = fit_layout((size_t)bp.n, (size_t)cfg.n_steps + 2, (size_t)n_psi, false);
+    // launch_plan's rule for 16 lanes per ray, on the padded lanes: whole waves per beam
+    size_t waves16 = 0;
+    for (int b = 0; b < n_beams; b++) waves16 += (size_t)(beam_off[b + 1] - beam_off[b] + 3) / 4;
+    const bool lanes16 = cfg.absorption == 1 && bp.DM != kDepoBinned && kn.lanes_per_ray != 1 &&
+                         (kn.lanes_per_ray == 16 ||
+                          (kn.lpr_env != 1 && waves16 * 64 <= (size_t)kn.n_cu * 4 * 2 * 64));
+    bp.lpr = lanes16 ? 16 : 1;
+    const int rpw = 64 / bp.lpr;  // rays per wave
+    bp.beams = beams_records(n_beams, beam_off, omega, mode);
+    for (int b = 0; b < n_beams; b++)
+        for (int i = beam_off[b]; i < beam_off[b + 1]; i += rpw) bp.waves.push_back(BeamWave{b, i});
+    return 0;
+}
+
 #ifndef TORJ_LAUNCH_PLAN_ONLY
 #include <mutex>
 
 #include "torj_dispatch.hpp"
+#include "torj_k_beams.hpp"
 #include "torj_k_fused.hpp"
 #include "torj_k_points.hpp"
 #include "torj_split.hpp"
@@ -382,6 +467,105 @@ static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, c
     HIPCK(hipGetLastError());
     if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
     if (pl.fit && launch_post(a, fa, pl, dstr, s)) return -1;
+    if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
+    return 0;
+}
+
+// ---- a multi-beam launch (torj_trace_beams_device, torj_ray_entry_beams_device) ----
+// the plan's tables into the handle's buffer, in `s`'s order: the beams' records, then
+// the waves'.  The copy is from pageable memory, which HIP has consumed when the call
+// returns; the buffer is the handle's scratch (one stream per handle), so a launch
+// enqueued earlier on `s` has read its own tables before these arrive.
+static int beams_upload(torj_plasma_s *p, const std::vector<BeamRec> &beams, const std::vector<BeamWave> &waves,
+                        hipStream_t s, const BeamRec **d_beams, const BeamWave **d_waves) {
+    const size_t nb = beams.size() * sizeof(BeamRec), nw = waves.size() * sizeof(BeamWave);
+    if (ensure_buf(p, p->beams, nb + nw)) return -1;
+    char *d = (char *)p->beams.d;
+    HIPCK(hipMemcpyAsync(d, beams.data(), nb, hipMemcpyHostToDevice, s));
+    if (nw) HIPCK(hipMemcpyAsync(d + nb, waves.data(), nw, hipMemcpyHostToDevice, s));
+    *d_beams = (const BeamRec *)d;
+    if (d_waves) *d_waves = (const BeamWave *)(d + nb);
+    return 0;
+}
+
+// k_trace_beams' instance: k_trace's set (launch_lanes)
+static void launch_beams(const BeamsArgs &ba, const BeamsPlan &bp, hipStream_t s) {
+    const dim3 grd((unsigned)bp.waves.size()), blk(64);
+    if (bp.lpr == 16)
+        with_depo_traj(bp.DM, bp.tr, [&](auto D, auto T) {
+            if constexpr (D() != kDepoBinned) hipLaunchKernelGGL((k_trace_beams<1, D(), T(), 16>), grd, blk, 0, s, ba);
+        });
+    else
+        with_abs_depo_traj(ba.a.abs_model == 1 ? 1 : 0, bp.DM, bp.tr, [&](auto A, auto D, auto T) {
+            if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace_beams<A(), D(), T()>), grd, blk, 0, s, ba);
+        });
+}
+
+// one multi-beam launch on stream `s` (the body of torj_trace_beams_device); the
+// three host tables are consumed before it returns
+static int beams_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+                              const double *omega, const int *mode, const double *x0, const double *N0,
+                              const double *weights, int n_psi, const double *grid, const double *x_launch,
+                              const double *s0, double *state, int *status, int *steps, double *dP,
+                              double *Pdep, double *traj, uint64_t *counters, hipStream_t s) {
+    const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
+                            x_launch != nullptr, s0 != nullptr, traj != nullptr};
+    BeamsPlan bp;
+    const bool fresh = !p->d_flags;  // n_cu is the device's only once ensure_device has run
+    if (beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+    if (ensure_device(p)) return -1;
+    if (fresh && beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+    const int n = bp.n;
+    if (n == 0) return 0;
+    if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
+    if (bp.fit) {
+        const size_t budget = ws_budget(p);
+        if (bp.lay.bytes() > budget)
+            return fail("multi-beam launch: the reference deposition's workspace for %d rays (%zu bytes) exceeds "
+                        "the budget of %zu bytes (TORJ_WS_GB); trace the beams in separate calls",
+                        n, bp.lay.bytes(), budget);
+    }
+    BeamsArgs ba{};
+    torj_trace_cfg c1 = *cfg;  // (omega and mode are the beams'; any valid pair here)
+    c1.omega = omega[0], c1.mode = mode[0];
+    TraceArgs &a = ba.a = trace_args(p, c1, n, x0, N0, weights, s0, state, status, steps, counters);
+    ba.n_beams = n_beams;
+    if (beams_upload(p, bp.beams, bp.waves, s, &ba.beams, &ba.waves)) return -1;
+    if (bp.depo) {
+        a.n_psi = n_psi, a.grid = grid, a.dP = dP;
+        if (!Pdep) {
+            if (ensure_buf(p, p->ws, (size_t)n * sizeof(double))) return -1;
+            Pdep = (double *)p->ws.d;
+        }
+        a.Pdep = Pdep;
+    }
+    FitArgs fa{};
+    if (bp.fit) {
+        if (ensure_buf(p, p->fit, bp.lay.bytes())) return -1;
+        fit_point(bp.lay, (char *)p->fit.d, fa, &a);
+        fit_args(fa, a, x_launch, true);
+    }
+    if (bp.depo) hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
+    if (bp.tr) {
+        a.traj_stride = cfg->traj_stride, a.n_save = bp.n_save, a.traj = traj;
+        if (a.n_save > 0)
+            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * n * sizeof(double), s));  // NaN
+    }
+    if (bp.fit && fit_zero(fa, s)) return -1;
+    hipEvent_t ev[3];
+    if (timing_begin(p, ev, s)) return -1;
+    launch_beams(ba, bp, s);
+    HIPCK(hipGetLastError());
+    if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
+    if (bp.fit) {  // launch_post with the beams' kernels
+        const dim3 grd(nblocks(n, 64)), blk(64);
+        with_abs(a.abs_model, [&](auto A) {
+            if constexpr (A() <= 1) hipLaunchKernelGGL(k_final_alpha_beams<A()>, grd, blk, 0, s, ba);
+        });
+        hipLaunchKernelGGL(k_fit_depo, grd, blk, fit_grid_lds(fa.n_psi), s, fa);
+        hipLaunchKernelGGL(k_shell_sum_beams, dim3(fa.n_psi, n_beams), dim3(256), 0, s, fa, ba.beams);
+        HIPCK(hipGetLastError());
+    }
     if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
     return 0;
 }

@@ -143,6 +143,7 @@ struct torj_plasma_s {
     std::vector<hipEvent_t> ev_pool;       // 3 per recorded call (start, trace end, post end)
     size_t ev_used = 0;
     GrowBuf ws;                    // per-ray workspace (double: P_dep when the caller passes none)
+    GrowBuf beams;                 // a multi-beam launch's beam and wave tables (BeamRec, BeamWave)
     // sticky launch error flags, ORed by every launch since the last
     // torj_trace_check (which reads and clears them): bit 0 psi grid not
     // strictly increasing, bit 1 work-queue watchdog, bit 2 unretired groups

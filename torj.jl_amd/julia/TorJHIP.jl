@@ -206,16 +206,10 @@ function make_ray(p::GPUPlasma, x0::AbstractVector, N_vacuum::AbstractVector, f:
 end
 make_ray(p::TorJ.Plasma, args...; kw...) = make_ray(gpu_plasma(p), args...; kw...)
 
-"""make_beam -- same signature and return tuple as TorJ.make_beam (src/solve.jl:209-242);
-the launch fan and IMAS angles on the host, every ray on the GPU(s): n_gpus devices of
-this process (torj_trace_beam), dP_shell summed across them by RCCL.  traj_stride keeps
-every traj_stride-th step of each ray (1 = all, as the reference) plus its final state."""
-function make_beam(p::GPUPlasma, r, phi, z, tor, pol, spot, inv_curv, f, mode::Integer,
-                   s_max::Float64, psi_dP_dV::Vector{Float64}; ds::Float64=1e-4,
-                   N_rings::Integer=3, min_azimuthal_points::Integer=5,
-                   normalize_weight_sum::Bool=true, deposition::Integer=1,
-                   integrator::Integer=0, absorption::Integer=1, traj_stride::Integer=1,
-                   n_gpus::Integer=1)
+# a launcher's fan (make_beam, make_beams): the IMAS angles to a direction, then
+# launch_peripheral_rays from (r, phi, z) -- positions and directions n x 3, weights n
+function _launch_fan(r, phi, z, tor, pol, spot, inv_curv, f, N_rings, min_azimuthal_points,
+                     normalize_weight_sum)
     N0 = zeros(3)
     ccall((:torj_pol_tor_angles_2_vector, libtorj), Cvoid, (Float64, Float64, Ptr{Float64}),
           pol, tor, N0)
@@ -233,6 +227,22 @@ function make_beam(p::GPUPlasma, r, phi, z, tor, pol, spot, inv_curv, f, mode::I
                  Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                 x0, N0, spot, inv_curv, f, N_rings, min_azimuthal_points, normalize_weight_sum, nr,
                 pos, dirs, w))
+    return pos, dirs, w
+end
+
+"""make_beam -- same signature and return tuple as TorJ.make_beam (src/solve.jl:209-242);
+the launch fan and IMAS angles on the host, every ray on the GPU(s): n_gpus devices of
+this process (torj_trace_beam), dP_shell summed across them by RCCL.  traj_stride keeps
+every traj_stride-th step of each ray (1 = all, as the reference) plus its final state."""
+function make_beam(p::GPUPlasma, r, phi, z, tor, pol, spot, inv_curv, f, mode::Integer,
+                   s_max::Float64, psi_dP_dV::Vector{Float64}; ds::Float64=1e-4,
+                   N_rings::Integer=3, min_azimuthal_points::Integer=5,
+                   normalize_weight_sum::Bool=true, deposition::Integer=1,
+                   integrator::Integer=0, absorption::Integer=1, traj_stride::Integer=1,
+                   n_gpus::Integer=1)
+    pos, dirs, w = _launch_fan(r, phi, z, tor, pol, spot, inv_curv, f, N_rings, min_azimuthal_points,
+                               normalize_weight_sum)
+    n = length(w)
     ω = 2π * f
     xp, Np, s0, st = ray_entry(p, pos, dirs, ω, mode)
     all(st .== 0) || throw(AssertionError("ray entry failed for $(count(st .!= 0)) rays"))
@@ -263,6 +273,95 @@ function make_beam(p::GPUPlasma, r, phi, z, tor, pol, spot, inv_curv, f, mode::I
     return arc_lengths, trajectories, ray_powers, dP_dV, dP[end], w
 end
 make_beam(p::TorJ.Plasma, args...; kw...) = make_beam(gpu_plasma(p), args...; kw...)
+
+# ---- many beams of differing frequency and mode in one launch (torj_trace_beams) ----
+# beam b owns rays beam_off[b] + 1 : beam_off[b + 1] (beam_off: 0-based offsets, length B + 1)
+
+"""ray_entry for the concatenated rays of B beams, ray i with its beam's omega and mode."""
+function ray_entry_beams(p::GPUPlasma, beam_off::Vector{Cint}, omega::Vector{Float64},
+                         mode::Vector{Cint}, x0::Matrix{Float64}, N0::Matrix{Float64})
+    n = size(x0, 1)
+    xp, Np, s0, st = zeros(n, 3), zeros(n, 3), zeros(n), zeros(Cint, n)
+    check(ccall((:torj_ray_entry_beams_gpu, libtorj), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                p.h, length(omega), beam_off, omega, mode, x0, N0, xp, Np, s0, st))
+    return xp, Np, s0, st
+end
+
+"""trace for B beams in one launch: cfg.omega and cfg.mode are ignored, dP has one row of
+length(psi_grid) + 1 per beam (returned as a (length(psi_grid) + 1) x B matrix)."""
+function trace_beams(p::GPUPlasma, cfg::TraceCfg, beam_off::Vector{Cint}, omega::Vector{Float64},
+                     mode::Vector{Cint}, x0::Matrix{Float64}, N0::Matrix{Float64},
+                     w::Vector{Float64}, psi_grid::Vector{Float64}, x_launch::Matrix{Float64},
+                     s0::Vector{Float64})
+    n, B = size(x0, 1), length(omega)
+    n_save = cfg.traj_stride > 0 ? cfg.n_steps ÷ cfg.traj_stride : 0
+    state, status, steps = zeros(n, 7), zeros(Cint, n), zeros(Cint, n)
+    dP, Pdep = zeros(length(psi_grid) + 1, B), zeros(n)
+    traj = n_save > 0 ? zeros(n, 5, n_save) : zeros(0, 5, 0)
+    GC.@preserve beam_off omega mode x0 N0 w psi_grid x_launch s0 begin
+        check(ccall((:torj_trace_beams, libtorj), Cint,
+                    (Ptr{Cvoid}, Ref{TraceCfg}, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    p.h, cfg, B, beam_off, omega, mode, x0, N0, w, length(psi_grid), psi_grid,
+                    x_launch, s0, state, status, steps, dP, Pdep, n_save > 0 ? traj : C_NULL))
+    end
+    return state, status, steps, dP, Pdep, traj
+end
+
+"""make_beams(plasma, launchers, s_max, psi_dP_dV; ...) -- one make_beam tuple per launcher,
+every launcher's rays in ONE launch.  `launchers`: tuples (r, phi, z, tor, pol, spot, inv_curv,
+f, mode), make_beam's leading arguments."""
+function make_beams(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{Float64};
+                    ds::Float64=1e-4, N_rings::Integer=3, min_azimuthal_points::Integer=5,
+                    normalize_weight_sum::Bool=true, deposition::Integer=1, absorption::Integer=1,
+                    traj_stride::Integer=1)
+    traj_stride >= 1 || throw(ArgumentError("traj_stride must be >= 1"))
+    B = length(launchers)
+    beam_off, omega, mode = zeros(Cint, B + 1), zeros(B), zeros(Cint, B)
+    fans = Vector{NTuple{3,Array{Float64}}}()
+    for (b, (r, phi, z, tor, pol, spot, inv_curv, f, m)) in enumerate(launchers)
+        pos, dirs, w = _launch_fan(r, phi, z, tor, pol, spot, inv_curv, f, N_rings, min_azimuthal_points,
+                                   normalize_weight_sum)
+        nr = length(w)
+        push!(fans, (pos, dirs, w))
+        beam_off[b + 1] = beam_off[b] + nr
+        omega[b], mode[b] = 2π * f, m
+    end
+    pos, dirs, w = vcat((a[1] for a in fans)...), vcat((a[2] for a in fans)...), vcat((a[3] for a in fans)...)
+    xp, Np, s0, st = ray_entry_beams(p, beam_off, omega, mode, pos, dirs)
+    for b in 1:B
+        bad = count(st[beam_off[b]+1:beam_off[b+1]] .!= 0)
+        bad == 0 || throw(AssertionError("beam $b: ray entry failed for $bad rays"))
+    end
+    n_steps = max(1, round(Int, s_max / ds))
+    cfg = TraceCfg(omega[1], mode[1], ds, n_steps, max(1, n_steps ÷ 100), 1.0, 1e-6, absorption,
+                   traj_stride, deposition, 0, 1e-6, 1e-6, s_max, 100)
+    state, status, steps, dP, Pdep, traj = trace_beams(p, cfg, beam_off, omega, mode, xp, Np, w,
+                                                        psi_dP_dV, pos, s0)
+    dV = shell_volumes(p, psi_dP_dV)
+    out = []
+    for b in 1:B
+        dP_dV = zeros(length(psi_dP_dV))
+        dP_dV[1:end-1] .= dP[1:end-2, b] ./ dV
+        arc_lengths, trajectories, ray_powers = Vector{Vector{Float64}}(), Vector{Vector{Vector{Float64}}}(), Vector{Vector{Float64}}()
+        for i in beam_off[b]+1:beam_off[b+1]
+            k = steps[i] ÷ traj_stride
+            s_i, x_i, τ_i = traj[i, 5, 1:k], [traj[i, 1:3, j] for j in 1:k], traj[i, 4, 1:k]
+            if steps[i] % traj_stride != 0  # the final state is not a saved sample
+                push!(s_i, fma(Float64(steps[i]), ds, s0[i])); push!(x_i, state[i, 1:3]); push!(τ_i, state[i, 7])
+            end
+            push!(arc_lengths, vcat(0.0, s0[i], s_i))
+            push!(trajectories, vcat([pos[i, :]], [xp[i, :]], x_i))
+            push!(ray_powers, vcat(1.0, 1.0, exp.(-τ_i)))
+        end
+        push!(out, (arc_lengths, trajectories, ray_powers, dP_dV, dP[end, b], w[beam_off[b]+1:beam_off[b+1]]))
+    end
+    return out
+end
+make_beams(p::TorJ.Plasma, args...; kw...) = make_beams(gpu_plasma(p), args...; kw...)
 
 """alpha(...) of src/general_absorption.jl:1328-1337 (repaired, DESIGN.md §3.6) at n
 points on the GPU: iwarm 1 (weakly) or 3 (fully relativistic); inv_dDdN = 1/|dD/dN|.

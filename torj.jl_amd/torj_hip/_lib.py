@@ -102,6 +102,14 @@ _SIGS = {
                                     C.c_void_p, C.c_void_p]),
     "torj_trace_device_ex": (C.c_int, [C.c_void_p, C.POINTER(TraceCfg), C.c_int] +
                              [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 11),
+    # many beams in one launch: beam_off, omega, mode are host tables in both forms
+    "torj_trace_beams_device": (C.c_int, [C.c_void_p, C.POINTER(TraceCfg), C.c_int, _ip, _dp, _ip] +
+                                [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 11),
+    "torj_trace_beams": (C.c_int, [C.c_void_p, C.POINTER(TraceCfg), C.c_int, _ip, _dp, _ip, _dp, _dp,
+                                   _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp]),
+    "torj_ray_entry_beams_device": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _ip] + [C.c_void_p] * 7),
+    "torj_ray_entry_beams_gpu": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _ip, _dp, _dp, _dp, _dp, _dp,
+                                           _ip]),
     "torj_shell_volumes": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "torj_power_deposition_profile": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp,
                                                 _dp, _dp]),

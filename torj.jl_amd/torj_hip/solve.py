@@ -130,6 +130,71 @@ def _steps_for(s_max: float, ds: float) -> int:
     return max(1, int(round(s_max / ds)))
 
 
+def _beam_tables(beam_off, omega, mode):
+    """The three host tables of a multi-beam call: beam b owns rays
+    beam_off[b] .. beam_off[b + 1] - 1 and is traced with omega[b], mode[b]."""
+    off = np.ascontiguousarray(beam_off, dtype=np.int32)
+    om = f64(omega)
+    md = np.ascontiguousarray(mode, dtype=np.int32)
+    if off.ndim != 1 or om.ndim != 1 or md.ndim != 1 or len(om) != len(md) or len(off) != len(om) + 1:
+        raise ValueError("beam_off needs n_beams + 1 entries, omega and mode n_beams each")
+    return off, om, md
+
+
+def ray_entry_beams(plasma, beam_off, omega, mode, x0, N0):
+    """ray_entry(..., gpu=True) for the concatenated rays of several beams, ray i
+    with its beam's omega and mode, in one launch (torj_ray_entry_beams_gpu)."""
+    off, om, md = _beam_tables(beam_off, omega, mode)
+    xs, Ns = soa(x0), soa(N0)
+    n = xs.shape[1]
+    if len(off) and off[-1] != n:
+        raise ValueError(f"beam_off[-1] = {off[-1]}, but {n} rays given")
+    xp, Np = np.zeros((3, n)), np.zeros((3, n))
+    s0 = np.zeros(n)
+    st = np.zeros(n, dtype=np.int32)
+    check(lib().torj_ray_entry_beams_gpu(plasma.handle, len(om), iptr(off), dptr(om), iptr(md), dptr(xs),
+                                         dptr(Ns), dptr(xp), dptr(Np), dptr(s0), iptr(st)))
+    return xp.T.copy(), Np.T.copy(), s0, st
+
+
+def trace_beams(plasma, beam_off, omega, mode, x0, N0, *, ds: float = 1e-4, n_steps: int,
+                chunk_steps: int | None = None, psi_exit: float = 1.0, P_min: float = 1e-6,
+                absorption=True, psi_grid=None, weights=None, traj_stride: int = 0,
+                deposition: str = "binned", x_launch=None, s0=None) -> TraceResult:
+    """trace() for the concatenated rays of several beams in ONE launch
+    (torj_trace_beams): beam b owns rays beam_off[b] .. beam_off[b + 1] - 1 and
+    is traced with omega[b] and mode[b]; every other setting is shared.
+    dP_shell has shape (n_beams, n_psi + 1), row b beam b's.  Fixed-step RK4 with
+    absorption "none" or "albajar" only; per-ray results equal trace()'s on each
+    beam alone."""
+    off, om, md = _beam_tables(beam_off, omega, mode)
+    xs, Ns = soa(x0), soa(N0)
+    n = xs.shape[1]
+    if len(off) and off[-1] != n:
+        raise ValueError(f"beam_off[-1] = {off[-1]}, but {n} rays given")
+    if chunk_steps is None:
+        chunk_steps = max(1, n_steps // 100)
+    cfg = TraceCfg(0.0, 0, float(ds), int(n_steps), int(chunk_steps), float(psi_exit), float(P_min),
+                   _absorption_code(absorption), int(traj_stride), DEPOSITION[deposition])
+    xl = soa(x_launch) if x_launch is not None else None
+    sv = f64(s0) if s0 is not None else None
+    g = f64(psi_grid) if psi_grid is not None else np.zeros(0)
+    n_psi = len(g)
+    w = f64(weights) if weights is not None else None
+    state = np.zeros((7, n))
+    status = np.zeros(n, dtype=np.int32)
+    steps = np.zeros(n, dtype=np.int32)
+    dP = np.zeros((len(om), n_psi + 1))
+    Pdep = np.zeros(n)
+    n_save = n_steps // traj_stride if traj_stride > 0 else 0
+    traj = np.zeros((n_save, 5, n)) if n_save > 0 else None
+    check(lib().torj_trace_beams(plasma.handle, cfg, len(om), iptr(off), dptr(om), iptr(md), dptr(xs),
+                                 dptr(Ns), dptr(w), n_psi, dptr(g) if n_psi else None, dptr(xl), dptr(sv),
+                                 dptr(state), iptr(status), iptr(steps), dptr(dP), dptr(Pdep), dptr(traj)))
+    return TraceResult(state.T.copy(), status, steps, dP, Pdep,
+                       traj.transpose(2, 0, 1).copy() if traj is not None else None)
+
+
 def make_ray(plasma, x0, N_vacuum, f: float, mode: int, s_max: float, psi_dP_dV, *,
              ds: float = 1e-4, deposition: str = "reference", integrator: str = "rk4",
              max_steps: int | None = None, absorption="albajar"):
@@ -178,6 +243,25 @@ def _final_arc_length(res, i, s0, ds):
     return fma(float(int(res.steps[i])), float(ds), float(s0))
 
 
+def _ray_lists(res, rays, pos, xp, s0, ds, traj_stride):
+    """make_beam's per-ray lists (arc lengths, trajectories, powers) of the rays
+    `rays` of a TraceResult: the launch point, the entry point, the saved samples
+    and, where it is not one of them, the final state."""
+    arc_lengths, trajectories, ray_powers = [], [], []
+    for i in rays:
+        k = int(res.steps[i]) // traj_stride
+        s_i, x_i, tau_i = res.traj[i, :k, 4], res.traj[i, :k, :3], res.traj[i, :k, 3]
+        if int(res.steps[i]) % traj_stride:  # the final state is not a saved sample
+            s_end = _final_arc_length(res, i, s0[i], ds)
+            s_i = np.concatenate([s_i, [s_end]])
+            x_i = np.vstack([x_i, res.state[i, :3][None]])
+            tau_i = np.concatenate([tau_i, [res.state[i, 6]]])
+        arc_lengths.append(np.concatenate([[0.0, s0[i]], s_i]))
+        trajectories.append(np.vstack([pos[i][None], xp[i][None], x_i]))
+        ray_powers.append(np.concatenate([[1.0, 1.0], np.exp(-tau_i)]))
+    return arc_lengths, trajectories, ray_powers
+
+
 def make_beam(plasma, r: float, phi: float, z: float, steering_angle_tor: float,
               steering_angle_pol: float, spot_size: float, inverse_curvature_radius: float,
               f: float, mode: int, s_max: float, psi_dP_dV, *, ds: float = 1e-4,
@@ -216,16 +300,43 @@ def make_beam(plasma, r: float, phi: float, z: float, steering_angle_tor: float,
     dP_dV = np.zeros(len(g))
     dP_dV[:-1] = res.dP_shell[:len(g) - 1] / dV
     deposited_power = float(res.dP_shell[len(g)])
-    arc_lengths, trajectories, ray_powers = [], [], []
-    for i in range(len(w)):
-        k = int(res.steps[i]) // traj_stride
-        s_i, x_i, tau_i = res.traj[i, :k, 4], res.traj[i, :k, :3], res.traj[i, :k, 3]
-        if int(res.steps[i]) % traj_stride:  # the final state is not a saved sample
-            s_end = _final_arc_length(res, i, s0[i], ds)
-            s_i = np.concatenate([s_i, [s_end]])
-            x_i = np.vstack([x_i, res.state[i, :3][None]])
-            tau_i = np.concatenate([tau_i, [res.state[i, 6]]])
-        arc_lengths.append(np.concatenate([[0.0, s0[i]], s_i]))
-        trajectories.append(np.vstack([pos[i][None], xp[i][None], x_i]))
-        ray_powers.append(np.concatenate([[1.0, 1.0], np.exp(-tau_i)]))
+    arc_lengths, trajectories, ray_powers = _ray_lists(res, range(len(w)), pos, xp, s0, ds, traj_stride)
     return arc_lengths, trajectories, ray_powers, dP_dV, deposited_power, w
+
+
+def make_beams(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, traj_stride: int = 1,
+               deposition: str = "reference", absorption="albajar", **kwargs):
+    """make_beam for several launchers in ONE launch (torj_ray_entry_beams_gpu,
+    torj_trace_beams): `launchers` is a sequence of (r, phi, z, steering_angle_tor,
+    steering_angle_pol, spot_size, inverse_curvature_radius, f, mode), make_beam's
+    leading arguments; returns one make_beam tuple per launcher, equal to what
+    make_beam gives for it.  Fixed-step RK4, absorption "albajar" or "none";
+    kwargs go to launch_peripheral_rays.  Raises RayEntryError naming the beam
+    when a ray fails entry."""
+    fans, omega, mode, off = [], [], [], [0]
+    for (r, phi, z, tor, pol, spot, inv_curv, f, m) in launchers:
+        N0 = pol_tor_angles_2_vector(pol, tor)
+        x0 = np.array([r * np.cos(phi), r * np.sin(phi), z])
+        fans.append(launch_peripheral_rays(x0, N0, spot, inv_curv, f, **kwargs))
+        omega.append(2.0 * np.pi * f)
+        mode.append(int(m))
+        off.append(off[-1] + len(fans[-1][2]))
+    pos, dirs, w = (np.concatenate([fan[k] for fan in fans]) for k in range(3))
+    xp, Np, s0, st = ray_entry_beams(plasma, off, omega, mode, pos, dirs)
+    for b in range(len(fans)):
+        bad = np.flatnonzero(st[off[b]:off[b + 1]] != OK)
+        if len(bad):
+            raise RayEntryError(f"beam {b}: {len(bad)} rays failed entry, first: ray {bad[0]} "
+                                f"{STATUS_NAMES[st[off[b] + bad[0]]]}")
+    g = f64(psi_dP_dV)
+    res = trace_beams(plasma, off, omega, mode, xp, Np, ds=ds, n_steps=_steps_for(s_max, ds), psi_grid=g,
+                      weights=w, traj_stride=traj_stride, deposition=deposition, x_launch=pos, s0=s0,
+                      absorption=absorption)
+    dV = plasma.shell_volumes(g)
+    out = []
+    for b in range(len(fans)):
+        dP_dV = np.zeros(len(g))
+        dP_dV[:-1] = res.dP_shell[b, :len(g) - 1] / dV
+        lists = _ray_lists(res, range(off[b], off[b + 1]), pos, xp, s0, ds, traj_stride)
+        out.append((*lists, dP_dV, float(res.dP_shell[b, len(g)]), w[off[b]:off[b + 1]]))
+    return out
