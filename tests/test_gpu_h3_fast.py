@@ -28,13 +28,18 @@ def _with_env(T, env, fn):
         T.abs_Al_init(24)
 
 
-@pytest.mark.parametrize("sched", [3, 0])
+@pytest.mark.parametrize("sched", [3, 2, 0])
 @pytest.mark.parametrize("tiny", ["1e-20", "0"])
 def test_h3_fast_bit_identical(gpu, T, hplasma, tiny, sched):
     """TORJ_H3_FAST=0 against 1 on the inputs of test_zero_flags_bit_identical,
-    split (3) and fused (0), with the tiny-alpha skip and without it: below the
-    second harmonic the exact leg integrates harmonic 3, so waves there mix
-    integrating and dismissible lanes -- the case the all-or-nothing rule is for."""
+    split (3) and fused (2: sixteen lanes per ray; 0: one), with the tiny-alpha
+    skip and without it: below the second harmonic the exact leg integrates
+    harmonic 3, so waves there mix integrating and dismissible lanes -- the case
+    the all-or-nothing rule is for.  The one-lane fused kernels never take the
+    shortcut: ray_segment always passes `work` there, and the shortcut is for
+    calls without it, so the 0 leg pins only that fact.  In the 16-lane kernels
+    `work` is set on a ray's lane 0 alone and the shortcut is live on the other
+    15 (tests/test_gpu_skip_configs.py: where harmonic 3 is the absorbing one)."""
     pos, xp, Np, s0, w, om = _fan(T, hplasma)
     kw = dict(ds=1e-4, n_steps=3000, chunk_steps=30, weights=w, traj_stride=30, P_min=5e-2,
               psi_grid=np.linspace(0, 1, 500), deposition="reference", x_launch=pos, s0=s0)

@@ -55,9 +55,10 @@ def test_split_equals_fused(gpu, T, hplasma, deposition, traj, block):
 
 
 def test_split_termination_vs_oracle(gpu, T, hplasma, oplasma):
-    """ABSORBED (P_min raised so rays stop mid-block at chunk boundaries),
-    LEFT_PLASMA (rays launched outwards), O-mode; with the trajectory samples
-    past a stop NaN as in the fused kernel."""
+    """ABSORBED (P_min raised so rays stop mid-block at chunk boundaries) and
+    LEFT_PLASMA (rays launched outwards), X-mode, with the trajectory samples
+    past a stop NaN as in the fused kernel.  (O-mode on the split path:
+    configuration B of tests/test_gpu_skip_configs.py.)"""
     from test_gpu_parity import _compare_trace
 
     pos, xp, Np, s0, w, om = _fan(T, hplasma, n_rings=4)
@@ -105,28 +106,30 @@ def test_split_counters_match_fused(gpu, T, hplasma, zflag):
     out = []
     old = os.environ.get("TORJ_ALPHA_ZFLAG")
     os.environ["TORJ_ALPHA_ZFLAG"] = zflag
-    for sched in (0, 3):
-        state = torch.empty((7, n), dtype=torch.float64, device=dev)
-        st = torch.empty(n, dtype=torch.int32, device=dev)
-        k = torch.empty(n, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(8, dtype=torch.int64, device=dev)
-        cfg = T._lib.TraceCfg(om, 1, 1e-4, 1500, 15, 1.0, 1e-6, 1, 0)
-        stream = torch.cuda.current_stream(dev)
-        hplasma.set_sched(sched, 0)
-        try:
-            T._lib.check(T.lib().torj_trace_device(hplasma.handle, cfg, n, x0.data_ptr(),
-                                                   N0.data_ptr(), None, 0, None, state.data_ptr(),
-                                                   st.data_ptr(), k.data_ptr(), None, None, None,
-                                                   ctypes.c_void_p(cnt.data_ptr()),
-                                                   stream.cuda_stream))
-            T._lib.check(T.lib().torj_trace_check(hplasma.handle, stream.cuda_stream))
-        finally:
-            hplasma.set_sched(-1)
-        out.append((cnt.cpu().numpy(), state.cpu().numpy()))
-    if old is None:
-        os.environ.pop("TORJ_ALPHA_ZFLAG", None)
-    else:
-        os.environ["TORJ_ALPHA_ZFLAG"] = old
+    try:
+        for sched in (0, 3):
+            state = torch.empty((7, n), dtype=torch.float64, device=dev)
+            st = torch.empty(n, dtype=torch.int32, device=dev)
+            k = torch.empty(n, dtype=torch.int32, device=dev)
+            cnt = torch.zeros(8, dtype=torch.int64, device=dev)
+            cfg = T._lib.TraceCfg(om, 1, 1e-4, 1500, 15, 1.0, 1e-6, 1, 0)
+            stream = torch.cuda.current_stream(dev)
+            hplasma.set_sched(sched, 0)
+            try:
+                T._lib.check(T.lib().torj_trace_device(hplasma.handle, cfg, n, x0.data_ptr(),
+                                                       N0.data_ptr(), None, 0, None, state.data_ptr(),
+                                                       st.data_ptr(), k.data_ptr(), None, None, None,
+                                                       ctypes.c_void_p(cnt.data_ptr()),
+                                                       stream.cuda_stream))
+                T._lib.check(T.lib().torj_trace_check(hplasma.handle, stream.cuda_stream))
+            finally:
+                hplasma.set_sched(-1)
+            out.append((cnt.cpu().numpy(), state.cpu().numpy()))
+    finally:
+        if old is None:
+            os.environ.pop("TORJ_ALPHA_ZFLAG", None)
+        else:
+            os.environ["TORJ_ALPHA_ZFLAG"] = old
     (cf, sf), (cs, ss) = out
     if zflag == "0":
         assert np.array_equal(cf, cs), (cf, cs)
@@ -424,7 +427,7 @@ def test_negligible_harmonic_skip_bit_identical(gpu, T, hplasma):
     assert np.array_equal(cnts["1", 3], cnts["1", 0])
 
 
-def _trace_counted(T, hplasma, sched, xp, Np, om):
+def _trace_counted(T, hplasma, sched, xp, Np, om, mode=1):
     """One traced launch's work counters (torj_trace_device with a counters array)."""
     import ctypes
 
@@ -438,7 +441,7 @@ def _trace_counted(T, hplasma, sched, xp, Np, om):
     st = torch.empty(n, dtype=torch.int32, device=dev)
     k = torch.empty(n, dtype=torch.int32, device=dev)
     cnt = torch.zeros(8, dtype=torch.int64, device=dev)
-    cfg = T._lib.TraceCfg(om, 1, 1e-4, 2000, 20, 1.0, 1e-6, 1, 0)
+    cfg = T._lib.TraceCfg(om, mode, 1e-4, 2000, 20, 1.0, 1e-6, 1, 0)
     stream = torch.cuda.current_stream(dev)
     hplasma.set_sched(sched, 0)
     try:

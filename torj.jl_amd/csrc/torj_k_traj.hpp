@@ -48,52 +48,16 @@
 // on the resonance gamma - N_par u_par = m Y, |u_par| <= gamma) -- the early
 // settle of abs_albajar_fast_body (and its exact-zero test), which returns +0
 // there, decided for a whole block with relative margins of 1e-9 against
-// their roundings.  k_alpha_pts then writes 0 for a wave whose 64 rays all
+// their roundings, and only inside the ranges in which the body itself stays
+// finite: 1e-100 < Y < 1e100 (r = m Y / sqrt(1 - N_par^2) is squared), ln Te <
+// 300 (albajar_finish squares 1 / mu), N_perp^2 > 1e-9 |N|^2 and N_par^2 < 1 -
+// 1e-9 (1 - 1e-6 with TORJ_NODE_GAMMA_LIN 0, whose gamma_min^2 cancels r^2 /
+// (1 - N_par^2)); any NaN or infinite input refuses.  k_alpha_pts then writes 0 for a wave whose 64 rays all
 // carry the flag instead of evaluating it (42 % of its waves settle early on the
 // headline beam).
-struct ZBox {
-    double lte = -INFINITY, ylo = INFINITY, yhi = -INFINITY, np2 = -INFINITY, perp = INFINITY;
-    double chk = 0.0;  // stays 0 unless an input was NaN or infinite
-};
-// v_max_f64 / v_min_f64 as one instruction each: fmax / fmin would first
-// quiet both operands (two more v_max_f64 per call, 24 VALU per stage point
-// for the box instead of 12); NaN inputs are caught by chk, not by these
-__device__ __forceinline__ double zb_max(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double zb_min(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void zero_box_add(ZBox &b, double lnTe, double Y, double Npar, double N2) {
-    const double np2 = Npar * Npar;
-    b.lte = zb_max(b.lte, lnTe);
-    b.ylo = zb_min(b.ylo, Y);
-    b.yhi = zb_max(b.yhi, Y);
-    b.np2 = zb_max(b.np2, np2);
-    b.perp = zb_min(b.perp, fma(-1e-9, N2, N2 - np2));  // N_perp^2 with a relative margin
-    b.chk = fma((lnTe + Y) + (Npar + N2), 0.0, b.chk);  // NaN once any input is NaN or infinite
-}
-__device__ __forceinline__ bool zero_box_flag(const ZBox &b) {
-    if (!(b.chk == 0.0)) return false;
-    if (b.lte < 2.9957322735539909 - 1e-9) return true;  // every Te < 20 eV (ln 20)
-    if (!(b.ylo > 1e-200 && b.yhi < 1e200 && b.perp > 0.0 && b.np2 < 1.0 - 1e-9 && b.lte < 700.0))
-        return false;
-    constexpr double kMuTe = kMe * kC * kC / kE;  // mu Te (albajar_pre)
-    const double delta = 760.0 * (1.0 + 1e-9) * exp(b.lte) * (1.0 / kMuTe);  // 760 / mu_min
-    const double npm = sqrt(b.np2), sq = sqrt(1.0 - b.np2);
-    bool ok = true;
-#pragma unroll
-    for (int m = 2; m <= 3; m++) {
-        const bool absent = m * b.yhi * (1.0 + 1e-9) < sq * (1.0 - 1e-9);
-        const bool zero = m * b.ylo > (1.0 + delta) * (1.0 + npm) * (1.0 + 1e-9);
-        ok = ok && (absent || zero);
-    }
-    return ok;
-}
+// (ZBox, zero_box_add and zero_box_flag live in torj_math.hpp after
+// abs_albajar_fast_body, whose early settle they restate: host and device, so
+// that tests/test_skip_proofs_host.py can sweep them against it on CPU)
 
 // One cold RK4 step of ray_segment's arithmetic (plasma_point with ln Te, as
 // the absorbing kernels evaluate it); STORE: this step's alpha inputs -> ain.

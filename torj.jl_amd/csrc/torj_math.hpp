@@ -1681,6 +1681,71 @@ TORJ_HD double abs_albajar_fast_body(const GLTable &gl, double omega, double X, 
     }
     return albajar_finish(q, c_abs, X, omega);
 }
+
+// The alpha-input box of one ray over a block of the split pipeline (the proof
+// is stated at torj_k_traj.hpp, whose trajectory kernel fills the box;
+// k_alpha_pts reads the flag).  The 760 here and harm_geom's kZeroYmax are the
+// same threshold: tests/test_skip_proofs_host.py holds the flag to the body above.
+struct ZBox {
+    double lte = -INFINITY, ylo = INFINITY, yhi = -INFINITY, np2 = -INFINITY, perp = INFINITY;
+    double chk = 0.0;  // stays 0 unless an input was NaN or infinite
+};
+// v_max_f64 / v_min_f64 as one instruction each: fmax / fmin would first
+// quiet both operands (two more v_max_f64 per call, 24 VALU per stage point
+// for the box instead of 12); NaN inputs are caught by chk, not by these
+// (host builds, the CPU sweep of tests/test_skip_proofs_host.py: fmax / fmin)
+TORJ_HD double zb_max(double a, double b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return fmax(a, b);
+#endif
+}
+TORJ_HD double zb_min(double a, double b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return fmin(a, b);
+#endif
+}
+TORJ_HD void zero_box_add(ZBox &b, double lnTe, double Y, double Npar, double N2) {
+    const double np2 = Npar * Npar;
+    b.lte = zb_max(b.lte, lnTe);
+    b.ylo = zb_min(b.ylo, Y);
+    b.yhi = zb_max(b.yhi, Y);
+    b.np2 = zb_max(b.np2, np2);
+    b.perp = zb_min(b.perp, fma(-1e-9, N2, N2 - np2));  // N_perp^2 with a relative margin
+    b.chk = fma((lnTe + Y) + (Npar + N2), 0.0, b.chk);  // NaN once any input is NaN or infinite
+}
+TORJ_HD bool zero_box_flag(const ZBox &b) {
+    if (!(b.chk == 0.0)) return false;
+    if (b.lte < 2.9957322735539909 - 1e-9) return true;  // every Te < 20 eV (ln 20)
+    // The ranges in which the body itself is finite, so that its value is the
+    // zero promised here and not an overflow's NaN (tests/test_skip_proofs_host.py):
+    // r = m Y / sqrt(1 - N_par^2) is squared (Y < 1e100), albajar_finish squares
+    // 1 / mu (ln Te < 300), and the square-root form of the node exponent
+    // (TORJ_NODE_GAMMA_LIN 0) cancels r^2 / (1 - N_par^2) down to gamma_min^2,
+    // which costs it 4e-16 / (1 - N_par^2)^2 of its 2 % margin.
+    constexpr double kNp2Max = TORJ_NODE_GAMMA_LIN ? 1.0 - 1e-9 : 1.0 - 1e-6;
+    if (!(b.ylo > 1e-100 && b.yhi < 1e100 && b.perp > 0.0 && b.np2 < kNp2Max && b.lte < 300.0))
+        return false;
+    constexpr double kMuTe = kMe * kC * kC / kE;  // mu Te (albajar_pre)
+    const double delta = 760.0 * (1.0 + 1e-9) * exp(b.lte) * (1.0 / kMuTe);  // 760 / mu_min
+    const double npm = sqrt(b.np2), sq = sqrt(1.0 - b.np2);
+    bool ok = true;
+#pragma unroll
+    for (int m = 2; m <= 3; m++) {
+        const bool absent = m * b.yhi * (1.0 + 1e-9) < sq * (1.0 - 1e-9);
+        const bool zero = m * b.ylo > (1.0 + delta) * (1.0 + npm) * (1.0 + 1e-9);
+        ok = ok && (absent || zero);
+    }
+    return ok;
+}
+
 // the fused trace kernels' call (out of line there, see TORJ_ALB_ATTR); kernels
 // with nothing else to hold (the split path's alpha kernel) inline the body
 template <int LPR = 1>
