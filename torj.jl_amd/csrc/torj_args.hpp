@@ -104,6 +104,9 @@ struct SplitArgs {
     unsigned *defer_cnt;        // warm: their count (this block's slot, zeroed per launch)
     int defer_lrm;              // warm: points with lrm above this are deferred (3; TORJ_WARM_DEFER_LRM
                                 // lowers it: a test sends every point through the deferred path)
+    int zlatch;                 // the trajectory kernel's dead-box latch (traj_run; TORJ_ZBOX_LATCH=0 in the
+                                // environment turns it off).  In the struct's tail padding: the kernels'
+                                // arguments after a SplitArgs keep their offsets
 };
 
 // steps | status << 24: split launches need n_steps < kSplitMaxSteps (the

@@ -22,12 +22,13 @@ __device__ void cold_replay(const TraceArgs &a, const SplitArgs &sp, int i, doub
     ZBox zb;  // (unused: the replay stores no zero flags)
     for (int s = 0; s < k; s++) {
         double xn[3], Nn[3], psi;
+        double *o_run = ain_row(a, sp, 0, i);  // every step into row 0
         if (sp.traj_mode == kTrajCell)
-            cold_step<true, kTileNS, TileCell, true>(a, cg, sp, 0, i, x, N, xn, Nn, &psi, zb, false);
+            cold_step<true, kTileNS, TileCell, true>(a, cg, sp, 0, i, x, N, xn, Nn, &psi, zb, false, o_run);
         else if (sp.traj_mode == kTrajTile)
-            cold_step<true, kTileNS, TileCoef, true>(a, ng, sp, 0, i, x, N, xn, Nn, &psi, zb, false);
+            cold_step<true, kTileNS, TileCoef, true>(a, ng, sp, 0, i, x, N, xn, Nn, &psi, zb, false, o_run);
         else
-            cold_step<true, kNF, const double *, true>(a, a.coef, sp, 0, i, x, N, xn, Nn, &psi, zb, false);
+            cold_step<true, kNF, const double *, true>(a, a.coef, sp, 0, i, x, N, xn, Nn, &psi, zb, false, o_run);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             x[c] = xn[c];

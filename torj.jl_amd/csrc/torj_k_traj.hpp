@@ -59,6 +59,13 @@
 // abs_albajar_fast_body, whose early settle they restate: host and device, so
 // that tests/test_skip_proofs_host.py can sweep them against it on CPU)
 
+#ifndef TORJ_TRAJ_AIN_STEP
+#define TORJ_TRAJ_AIN_STEP 1
+#endif
+// row `row` of the block's alpha inputs (a row: one stage of one step, nf fields of n rays) at ray i
+__device__ __forceinline__ double *ain_row(const TraceArgs &a, const SplitArgs &sp, int row, int i) {
+    return sp.ain + ((size_t)row * sp.nf) * a.n + i;
+}
 // One cold RK4 step of ray_segment's arithmetic (plasma_point with ln Te, as
 // the absorbing kernels evaluate it); STORE: this step's alpha inputs -> ain.
 // PSI: stage 0's stencil also sums psi at x (the step's start), returned in
@@ -68,7 +75,7 @@ template <bool STORE, int NS = kNF, class CS = const double *, bool PSI = false>
 __device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
                                           const SplitArgs &sp, int j, int i, const double x[3],
                                           const double N[3], double xn[3], double Nn[3],
-                                          double *psi_x, ZBox &zb, bool zon) {
+                                          double *psi_x, ZBox &zb, bool zon, double *&o_run) {
     const double hds = 0.5 * a.ds, ds6 = a.ds / 6.0;
     double acc[6] = {0, 0, 0, 0, 0, 0}, xt[3], Nt[3], k[6];
 #pragma unroll
@@ -76,6 +83,14 @@ __device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
         xt[c] = x[c];
         Nt[c] = N[c];
     }
+    // the cell-tiled kernel's trims (round 11): stage st's alpha inputs go to ain
+    // + ((j * 4 + st) * nf) * n + i -- per stage a 64-bit product of a lane's j
+    // (two v_mul_lo_u32 and a v_mad_u64_u32, quarter rate) -- which is one row
+    // of nf * n further at every stage, step after step: the caller's pointer
+    // o_run, at row j * 4 on entry, moves on by a row per stage (ain_row;
+    // TORJ_TRAJ_AIN_STEP) and replaces j; and the dispersion's unused reciprocal
+    // sits behind a wave-uniform branch
+    constexpr bool kCellTrim = IsTileCell<CS>::value;
 #pragma unroll 1
     for (int st = 0; st < 4; st++) {
         PlasmaPoint p;
@@ -92,9 +107,15 @@ __device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
             plasma_point<true, NS>(coef, a.g, a.k, xt, p);
         }
         double Npar, inv;
-        dispersion_grad(p, Nt, a.mode, k, &Npar, &inv);
+        dispersion_grad<kCellTrim>(p, Nt, a.mode, k, &Npar, &inv);
         if constexpr (STORE) {
-            double *o = sp.ain + ((size_t)(j * 4 + st) * sp.nf) * a.n + i;
+            double *o;
+            if constexpr (kCellTrim && TORJ_TRAJ_AIN_STEP) {
+                o = o_run;
+                o_run += (size_t)sp.nf * a.n;
+            } else {
+                o = sp.ain + ((size_t)(j * 4 + st) * sp.nf) * a.n + i;
+            }
             const double N2 = Nt[0] * Nt[0] + Nt[1] * Nt[1] + Nt[2] * Nt[2];
             if (zon) zero_box_add(zb, p.lnTe, p.Y, Npar, N2);
             o[0] = p.X;
@@ -175,6 +196,19 @@ __device__ __forceinline__ int cell_index(double x, double x1, double xn, double
 #ifndef TORJ_TRAJ_PREWAIT
 #define TORJ_TRAJ_PREWAIT 1
 #endif
+// the dead-box latch of traj_run (0: never compiled in; 1: on unless
+// TORJ_ZBOX_LATCH=0 in the environment, read per call: SplitArgs::zlatch), and
+// the loop trips after which a wave looks at its boxes' flags
+#ifndef TORJ_ZBOX_LATCH
+#define TORJ_ZBOX_LATCH 1
+#endif
+#ifndef TORJ_ZLATCH_TRIP0
+#define TORJ_ZLATCH_TRIP0 1
+#endif
+#ifndef TORJ_ZLATCH_TRIP1
+#define TORJ_ZLATCH_TRIP1 16
+#endif
+constexpr int kZLatchTrip0 = TORJ_ZLATCH_TRIP0, kZLatchTrip1 = TORJ_ZLATCH_TRIP1;
 // the trajectory steps of one ray over the block, from its carry (x, N, steps)
 template <int DEPO, bool TRAJ, int NS, class CS>
 __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp, CS coef, int i,
@@ -209,7 +243,9 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
     // (a value and a flag, not a pointer: a local behind a conditional pointer
     // lived in scratch, 56 B per lane, and slowed the kernel by ~14 %)
     ZBox zb;
-    const bool zon = sp.zflag != nullptr;
+    bool zon = sp.zflag != nullptr;  // wave-uniform: the stages' branch around zero_box_add
+    const bool zlatch = TORJ_ZBOX_LATCH && zon && sp.zlatch != 0;
+    int trips = 0;  // of the wave's step loop (uniform, unlike s)
 #if defined(__HIP_DEVICE_COMPILE__) && TORJ_TRAJ_PREWAIT
     // every load before the step loop complete here (s_waitcnt vmcnt(0)): the
     // compiler otherwise waits at the loop header for the carry's loads, every
@@ -217,9 +253,10 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
     // its own last stage's alpha-input stores to reach memory
     __builtin_amdgcn_s_waitcnt(0x0F70);
 #endif
+    double *o_run = ain_row(a, sp, (s_first - sp.k0) * 4, i);  // cold_step's store pointer (the cell kernel)
     for (int s = s_first; s < s_end; s++) {
         double xn[3], Nn[3], psi_x;
-        const bool bad = cold_step<true, NS, CS, true>(a, coef, sp, s - sp.k0, i, x, N, xn, Nn, &psi_x, zb, zon);
+        const bool bad = cold_step<true, NS, CS, true>(a, coef, sp, s - sp.k0, i, x, N, xn, Nn, &psi_x, zb, zon, o_run);
         if (pending) {
             pending = false;
             if (step_end(s - 1, psi_x)) {
@@ -256,6 +293,25 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
                 cb[(3 + c) * (size_t)a.n] = N[c];
             }
         }
+        // The dead-box latch.  zero_box_flag is monotone: a further point only
+        // raises lte, yhi, np2 and chk's NaN and lowers ylo and perp, and each of
+        // its conditions only gets harder that way, so a box whose flag is false
+        // stays false to the end of the block (swept on the CPU by
+        // tests/test_zbox_latch_host.py).  Once no lane still in the loop has a
+        // true flag, the rest of the block's zero_box_add calls decide nothing:
+        // they stop, and these lanes' boxes are poisoned through chk so that they
+        // write flag 0.  A lane that left the loop earlier is not active here and
+        // keeps its own box.  Even off the proof the latch could only turn a 1
+        // into a 0, which k_alpha_pts answers by evaluating the zero.
+        if (zlatch && zon) {
+            trips++;
+            if (trips == kZLatchTrip0 || trips == kZLatchTrip1) {
+                if (!__any(zero_box_flag(zb))) {
+                    zero_box_kill(zb);
+                    zon = false;
+                }
+            }
+        }
     }
     double invR;
     if (pending && step_end(steps - 1, eval_one<NS>(coef, a.g, cyl_radius(x, invR), x[2], F_PSI)))
@@ -266,7 +322,7 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
         sp.tx[(3 + c) * (size_t)a.n + i] = N[c];
     }
     sp.tinfo[i] = make_info(steps, st);
-    if (zon) sp.zflag[i] = zero_box_flag(zb) ? 1 : 0;
+    if (sp.zflag != nullptr) sp.zflag[i] = zero_box_flag(zb) ? 1 : 0;
 }
 
 

@@ -161,7 +161,12 @@ TORJ_HD double sqrt_node(double x) {
 // with an SGPR operand do.  The empty asm is volatile so that it is neither
 // hoisted nor merged: the pair lives for one instruction.  For kernels with
 // SGPRs to spare only (k_alpha_pts: 103 of 106, no spills); the trajectory
-// kernel, at 106 with spills, keeps its constants hoisted in VGPRs.
+// kernel, at 106 with spills, keeps its constants hoisted in VGPRs.  (The
+// cell-tiled trajectory kernel, whose unit is compiled without machine LICM,
+// rebuilds its nine coefficient pairs by 18 v_mov_b32 at every stage; taking
+// them from SGPR pairs there was measured in round 11 and gained nothing -- the
+// moves issue in the shadow of the Horner chain's dependent fma -- and was
+// rejected: DESIGN.md 3.7.)
 #ifndef TORJ_EXP_SCONST
 #define TORJ_EXP_SCONST 1
 #endif
@@ -518,8 +523,46 @@ struct CellAxis {
     int i;
     double t, delta;  // t: the offset from the cell's corner in metres
 };
-// axis_setup's cell, fraction (times h) and Line() distance
+// axis_setup's cell, fraction (times h) and Line() distance.
+// TORJ_CELL_AXIS_FAST (device only; the host keeps the plain form): the
+// coordinate clamp as v_max_f64 / v_min_f64 and the index clamp as one
+// v_med3_i32 instead of a compare and two selects per side (as zb_max: inline
+// asm, since fmax / fmin would first quiet both operands).  The bounds sit in
+// the asm's scalar operand, so they must be wave-uniform: the grid's, which
+// are kernel arguments.  For a number x (x1 <= xn, both finite) min(max(x, x1),
+// xn) is clampd's value; the one exception is a zero of the other sign than a
+// bound that is itself a zero, where the clamp's zero may take the bound's
+// sign.  A NaN x comes out of v_max_f64 as x1 (or, a signalling one, as a quiet
+// NaN) where clampd passes it through: delta = x - xc is NaN either way, so
+// the point still counts as outside (cell_inside below) and every field value
+// of the extrapolating evaluation, v + dRx gR + dZx gZ, is NaN as before --
+// with them |B|, N_par and the whole RHS, and the step ends ST_NAN where it
+// did.  With xc a number, u >= +0, so the conversion's truncation is floor(u)
+// and v_floor_f64 goes; n >= 2 makes med3(i, 0, n - 2) the two-sided clamp.
+#ifndef TORJ_CELL_AXIS_FAST
+#define TORJ_CELL_AXIS_FAST 1
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && TORJ_CELL_AXIS_FAST
+constexpr bool kCellAxisFast = true;
+#else
+constexpr bool kCellAxisFast = false;
+#endif
 TORJ_HD void cell_axis(double x, double x1, double xn, double h, double invh, int n, CellAxis &a) {
+#if defined(__HIP_DEVICE_COMPILE__) && TORJ_CELL_AXIS_FAST
+    // x as a register of unknown origin: where it is a product in the caller (R =
+    // R2 * invR), x - xc below could be contracted to fma(R2, invR, -xc), which
+    // is the product's rounding error, not 0, at a point inside the grid
+    asm("" : "+v"(x));
+    double xc;
+    asm("v_max_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(x1));
+    asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(xc), "s"(xn));
+    a.delta = x - xc;
+    const double u = (xc - x1) * invh;
+    int i;
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(i) : "v"((int)u), "s"(n - 2));
+    a.t = (u - (double)i) * h;
+    a.i = i;
+#else
     const double xc = clampd(x, x1, xn);
     a.delta = x - xc;
     const double u = (xc - x1) * invh;
@@ -527,6 +570,7 @@ TORJ_HD void cell_axis(double x, double x1, double xn, double h, double invh, in
     i = i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
     a.t = (u - (double)i) * h;
     a.i = i;
+#endif
 }
 // A wave's tile of cell records staged in LDS: cells [cR0, cR0 + cw) x
 // [cZ0, cZ0 + ch), R fastest; g: the whole table ((nR - 1) x (nZ - 1) cells).
@@ -582,15 +626,17 @@ TORJ_HD void cell_sums(P c, const CellAxis &aR, const CellAxis &aZ, const int (&
         cell_field(A, tR, tZ, EXT || f < NGRAD, EXT && f < NGRAD, v[f], gr[f], gz[f], grz[f]);
     }
 }
+// (from the point's two axes, which plasma_point forms once for both the
+// inside test and the evaluation: cell_inside)
 template <int NGRAD, int NVAL, bool EXT = true, int NS = kNF>
-TORJ_HD void eval_fields(const TileCell &t, const Grid &g, double R, double Z,
+TORJ_HD void eval_fields(const TileCell &t, const Grid &g, const CellAxis &aR, const CellAxis &aZ,
                          const int (&fidx)[NGRAD + NVAL], FieldPack<NGRAD, NVAL> &out) {
     constexpr int NT = NGRAD + NVAL;
-    CellAxis aR, aZ;
-    cell_axis(R, g.R1, g.Rn, g.hR, g.invhR, g.nR, aR);
-    cell_axis(Z, g.Z1, g.Zn, g.hZ, g.invhZ, g.nZ, aZ);
     const int dR = aR.i - t.cR0, dZ = aZ.i - t.cZ0;
-    bool in = dR >= 0 && dR < t.cw && dZ >= 0 && dZ < t.ch;
+    // in the tile: 0 <= d < extent, as one unsigned compare per axis (the
+    // extents are >= 0; 0, no tile, admits nothing)
+    bool in = kCellAxisFast ? (unsigned)dR < (unsigned)t.cw && (unsigned)dZ < (unsigned)t.ch
+                            : dR >= 0 && dR < t.cw && dZ >= 0 && dZ < t.ch;
 #ifdef __HIP_DEVICE_COMPILE__
     in = __all(in);
     using LdsP = const __attribute__((address_space(3))) double *;
@@ -609,6 +655,14 @@ TORJ_HD void eval_fields(const TileCell &t, const Grid &g, double R, double Z,
         cell_sums<NGRAD, NVAL, EXT, GlbP>((GlbP)t.g + ((size_t)aZ.i * (g.nR - 1) + aR.i) * kCellRec, aR, aZ,
                                           fidx, v, gr, gz, grz);
     fields_finish_d<NGRAD, NVAL, EXT, true>(g, aR.delta, aZ.delta, v, gr, gz, grz, out);
+}
+template <int NGRAD, int NVAL, bool EXT = true, int NS = kNF>
+TORJ_HD void eval_fields(const TileCell &t, const Grid &g, double R, double Z,
+                         const int (&fidx)[NGRAD + NVAL], FieldPack<NGRAD, NVAL> &out) {
+    CellAxis aR, aZ;
+    cell_axis(R, g.R1, g.Rn, g.hR, g.invhR, g.nR, aR);
+    cell_axis(Z, g.Z1, g.Zn, g.hZ, g.invhZ, g.nZ, aZ);
+    eval_fields<NGRAD, NVAL, EXT, NS>(t, g, aR, aZ, fidx, out);
 }
 // the cell records of a plasma's node coefficients (kNF doubles per node,
 // (nR + 2) x (nZ + 2) nodes) -> (nR - 1) x (nZ - 1) x kCellRec doubles
@@ -649,15 +703,57 @@ TORJ_HD bool inside_grid(const Grid &g, double R, double Z) {
 #endif
 }
 
+// inside_grid from the cell path's axes: delta = x - clamp(x) is 0 exactly when
+// x1 <= x <= xn -- inside, the clamp returns x and x - x = 0; outside, x and the
+// bound it was clamped to are different numbers, whose difference is never 0
+// (fp64 keeps denormals); a NaN x gives a NaN delta, which is not 0, so it counts
+// as outside, as all four of inside_grid's compares fail on it.  Two compares
+// with zero instead of four with the bounds.  It needs delta to be the true
+// difference of x and its clamp: cell_axis keeps the subtraction from being
+// contracted with a product that made x (tests/test_gpu_traj_trim.py).
+TORJ_HD bool cell_inside(const CellAxis &aR, const CellAxis &aZ) {
+    const bool in = aR.delta == 0.0 && aZ.delta == 0.0;
+#ifdef __HIP_DEVICE_COMPILE__
+    return __all(in);
+#else
+    return in;
+#endif
+}
+template <class CS>
+struct IsTileCell {
+    static constexpr bool value = false;
+};
+template <>
+struct IsTileCell<TileCell> {
+    static constexpr bool value = true;
+};
+// eval_fields with or without the Line() extrapolation, as the point (on the
+// device: the wave's points) lies outside or inside the grid
+template <int NGRAD, int NVAL, int NS, class CS>
+TORJ_HD void eval_fields_at(CS coef, const Grid &g, double R, double Z, const int (&fidx)[NGRAD + NVAL],
+                            FieldPack<NGRAD, NVAL> &out) {
+    if constexpr (kCellAxisFast && IsTileCell<CS>::value) {
+        CellAxis aR, aZ;
+        cell_axis(R, g.R1, g.Rn, g.hR, g.invhR, g.nR, aR);
+        cell_axis(Z, g.Z1, g.Zn, g.hZ, g.invhZ, g.nZ, aZ);
+        if (cell_inside(aR, aZ))
+            eval_fields<NGRAD, NVAL, false, NS>(coef, g, aR, aZ, fidx, out);
+        else
+            eval_fields<NGRAD, NVAL, true, NS>(coef, g, aR, aZ, fidx, out);
+    } else {
+        if (inside_grid(g, R, Z))
+            eval_fields<NGRAD, NVAL, false, NS>(coef, g, R, Z, fidx, out);
+        else
+            eval_fields<NGRAD, NVAL, true, NS>(coef, g, R, Z, fidx, out);
+    }
+}
+
 // single value (e.g. psi for termination / deposition)
 template <int NS = kNF, class CS = const double *>
 TORJ_HD double eval_one(CS coef, const Grid &g, double R, double Z, int field) {
     FieldPack<0, 1> p;
     const int idx[1] = {field};
-    if (inside_grid(g, R, Z))
-        eval_fields<0, 1, false, NS>(coef, g, R, Z, idx, p);
-    else
-        eval_fields<0, 1, true, NS>(coef, g, R, Z, idx, p);
+    eval_fields_at<0, 1, NS>(coef, g, R, Z, idx, p);
     return p.v[0];
 }
 
@@ -691,8 +787,25 @@ struct NsPartials {
 
 // invY: 1 / Y when the caller has it (dispersion_grad: 1 / |B| times 1 / Cy),
 // else 0 (one reciprocal here)
+// WAVE (the cell-tiled trajectory kernel, TORJ_TRAJ_RCP_BRANCH): the reciprocal
+// behind a wave-uniform branch.  As a select it is evaluated at every call --
+// v_rcp_f64, four fma, a compare and two selects -- for a caller whose invY is
+// never 0 short of an underflow; the lanes that do need it get the same value.
+#ifndef TORJ_TRAJ_RCP_BRANCH
+#define TORJ_TRAJ_RCP_BRANCH 1
+#endif
+template <bool WAVE = false>
 TORJ_HD NsPartials refractive_index_sq_partials(double X, double Y, double Npar, int mode, double invY = 0.0) {
     const double md = (double)mode;
+#ifdef __HIP_DEVICE_COMPILE__
+    if constexpr (WAVE && TORJ_TRAJ_RCP_BRANCH) {
+        if (__any(invY == 0.0)) {
+            // (volatile: the compiler otherwise speculates the block and selects again)
+            asm volatile("; 1 / Y for a lane without it");
+            if (invY == 0.0) invY = rcp_nz(Y);
+        }
+    } else
+#endif
     if (invY == 0.0) invY = rcp_nz(Y);
     const double Np2 = Npar * Npar, Y2 = Y * Y, invY2 = invY * invY;
     const double om = 1.0 - Np2, omX = 1.0 - X;
@@ -780,28 +893,18 @@ TORJ_HD void plasma_point(CS coef, const Grid &g, const Consts &k,
     const double c = x[0] * invR, s = x[1] * invR;
     constexpr int NV = WITH_TE ? (WITH_PSI ? 2 : 1) : 0;
     FieldPack<4, NV> f;
-    const bool in = inside_grid(g, R, x[2]);
     if constexpr (WITH_PSI) {
         const int idx[6] = {F_BR, F_BPHI, F_BZ, F_LNNE, F_LNTE, F_PSI};
-        if (in)
-            eval_fields<4, 2, false, NS>(coef, g, R, x[2], idx, f);
-        else
-            eval_fields<4, 2, true, NS>(coef, g, R, x[2], idx, f);
+        eval_fields_at<4, 2, NS>(coef, g, R, x[2], idx, f);
         p.lnTe = f.v[4];
         p.psi = f.v[5];
     } else if constexpr (WITH_TE) {
         const int idx[5] = {F_BR, F_BPHI, F_BZ, F_LNNE, F_LNTE};
-        if (in)
-            eval_fields<4, 1, false, NS>(coef, g, R, x[2], idx, f);
-        else
-            eval_fields<4, 1, true, NS>(coef, g, R, x[2], idx, f);
+        eval_fields_at<4, 1, NS>(coef, g, R, x[2], idx, f);
         p.lnTe = f.v[4];
     } else {
         const int idx[4] = {F_BR, F_BPHI, F_BZ, F_LNNE};
-        if (in)
-            eval_fields<4, 0, false, NS>(coef, g, R, x[2], idx, f);
-        else
-            eval_fields<4, 0, true, NS>(coef, g, R, x[2], idx, f);
+        eval_fields_at<4, 0, NS>(coef, g, R, x[2], idx, f);
         p.lnTe = 0.0;
     }
     const double Br = f.v[0], Bp = f.v[1], Bz = f.v[2];
@@ -851,10 +954,12 @@ TORJ_HD void plasma_point(CS coef, const Grid &g, const Consts &k,
 // of (N_R, N_phi, N_Z) with d/dR, d/dZ of (B_R, B_phi, B_Z) and
 // W = (N_R B_phi - N_phi B_R) / R.  So every x-gradient is (c A_R + s A_W,
 // s A_R - c A_W, A_Z): ~30 VALU per RHS fewer than the rotated 3 x 3 Jacobian.
+// (WAVE: refractive_index_sq_partials' wave-uniform branch)
+template <bool WAVE = false>
 TORJ_HD double dispersion_grad(const PlasmaPoint &p, const double N[3], int mode, double du[6],
                                double *Npar_out, double *inv_out = nullptr) {
     const double Npar = N[0] * p.b[0] + N[1] * p.b[1] + N[2] * p.b[2];
-    const NsPartials ns = refractive_index_sq_partials(p.X, p.Y, Npar, mode, p.invB * p.invCy);
+    const NsPartials ns = refractive_index_sq_partials<WAVE>(p.X, p.Y, Npar, mode, p.invB * p.invCy);
     const double N2 = N[0] * N[0] + N[1] * N[1] + N[2] * N[2];
     double dDdN[3];
 #pragma unroll
@@ -1745,6 +1850,9 @@ TORJ_HD bool zero_box_flag(const ZBox &b) {
     }
     return ok;
 }
+// A box given up for the rest of its block (traj_run's dead-box latch): the
+// flag is false from here on, whatever is added.
+TORJ_HD void zero_box_kill(ZBox &b) { b.chk = NAN; }
 
 // the fused trace kernels' call (out of line there, see TORJ_ALB_ATTR); kernels
 // with nothing else to hold (the split path's alpha kernel) inline the body

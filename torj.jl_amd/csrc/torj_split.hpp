@@ -36,7 +36,7 @@ struct SplitPlan {
     int n_blk;
     size_t b_ain, b_alpha, b_awork, b_psib, b_cbx, b_n8, b_n4, b_zf, b_dsd, b_dsi, b_defer, b_dcnt, bytes;
     bool zflag_on, dstream, serial;
-    int dstream_env, depo_lag, lds_env, tile_cap, nan_step, zflag_nan_from, defer_lrm;
+    int dstream_env, depo_lag, lds_env, tile_cap, nan_step, zflag_nan_from, defer_lrm, zlatch;
     double tile_margin;
 
     int block_k0(int b) const { return (int)(first ? (b == 0 ? 0 : first + (long)(b - 1) * kb) : b * kb); }
@@ -84,6 +84,9 @@ static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a,
     // TORJ_ALPHA_ZFLAG=0 (read per call) turns them off
     pl.zflag_on = a.abs_model == 1 && negl_skip && env_int("TORJ_ALPHA_ZFLAG", 1) != 0;
     pl.b_zf = pl.zflag_on ? al(n) : 0;
+    // TORJ_ZBOX_LATCH=0 (read per call): the trajectory kernel keeps growing every
+    // ray's box to the end of the block (traj_run's latch; the flags are the same)
+    pl.zlatch = env_int("TORJ_ZBOX_LATCH", 1) != 0;
     // the streamed deposition's per-ray walk state (fa: the reference profile;
     // TORJ_DEPO_STREAM=0 runs the whole walk after the trace instead)
     // TORJ_DEPO_STREAM=1: the windows on the scan's stream, after each scan;
@@ -218,6 +221,7 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
     sp.nan_step = pl.nan_step;
     sp.zval = 0.0;
     sp.defer_lrm = pl.defer_lrm;
+    sp.zlatch = pl.zlatch;
 
     const bool serial = pl.serial, dstream = pl.dstream;
     // the scan on a third stream (TORJ_SPLIT_SCAN=0: behind the alpha kernel on
