@@ -39,7 +39,10 @@ extern "C" {
                                6: torj_beam_timing_read, torj_trace_beam's automatic shards;
                                7: torj_build_id; 8: torj_beam_comm_info; still 8 (symbols added,
                                nothing changed): torj_trace_beams, torj_trace_beams_device,
-                               torj_ray_entry_beams_gpu, torj_ray_entry_beams_device */
+                               torj_ray_entry_beams_gpu, torj_ray_entry_beams_device;
+                               still 8 (four more symbols, nothing changed):
+                               torj_trace_beams_plasmas, torj_trace_beams_plasmas_device,
+                               torj_ray_entry_beams_plasmas_gpu, torj_ray_entry_beams_plasmas_device */
 
 /* per-ray status codes (replace the reference's @assert / unhandled returns) */
 enum torj_status {
@@ -293,6 +296,60 @@ int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off,
                              const double *omega, const int *mode, const double *x0,
                              const double *N0, double *x_plasma, double *N_plasma, double *s0,
                              int *status);
+
+/* ---- many small beams through differing plasmas in one launch -------------
+ * The multi-beam calls above with a plasma per beam: every time slice of a
+ * pulse, a density or temperature scan, an ensemble of perturbed equilibria,
+ * each a handful of small beams, share one launch instead of one launch per
+ * plasma.  Beam b is traced through plasmas[beam_plasma[b]], 0 <= beam_plasma[b]
+ * < n_plasmas <= 4096; a plasma may be listed twice or used by no beam, and the
+ * plasmas' grids (nR, nZ, ranges) may differ.  The ray entry uses each plasma's
+ * own psi_prof_max.  cfg, psi_exit included, and psi_grid are shared.
+ * p is the launch's handle as in every other call: it gives the stream of a
+ * NULL `stream`, the scratch buffers and the workspace budget, the sticky flags
+ * torj_trace_check(p, ...) reads, torj_timing and the torj_set_sched knobs
+ * (lanes per ray are chosen on the whole launch, as above).  p may be listed or
+ * not; its own plasma is used only by beams that name it.  Every listed handle
+ * must be on p's device (another device is refused, not supported).
+ * plasmas and beam_plasma are HOST arrays in both forms (n_plasmas, n_beams),
+ * consumed before the call returns like beam_off, omega and mode.
+ * Lifetime: the enqueued kernels read the listed handles' device coefficients.
+ * Destroying a listed handle before torj_trace_check(p, stream) (or a
+ * synchronisation of the stream) has returned is a caller error, the same rule
+ * as for every device pointer of the call.  A listed handle never used on the
+ * GPU before gets its device state here (allocations and a synchronous upload
+ * of its coefficients, once).
+ * Results: every per-ray output, and with deposition = 1 row b of dP_shell,
+ * equals bit for bit what torj_trace_device_ex gives for beam b alone on
+ * plasmas[beam_plasma[b]] with the same lanes per ray; with n_plasmas = 1 the
+ * call is torj_trace_beams_device on that plasma.  Restrictions as above:
+ * absorption 0 / 1, integrator 0, torj_set_sched -1 / 0 / 2, no ray batches. */
+int torj_trace_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                                    const int *beam_plasma, const torj_trace_cfg *cfg, int n_beams,
+                                    const int *beam_off, const double *omega, const int *mode,
+                                    const double *x0, const double *N0, const double *weights,
+                                    int n_psi, const double *psi_grid, const double *x_launch,
+                                    const double *s0, double *state, int *status, int *steps,
+                                    double *dP_shell, double *P_dep, double *traj,
+                                    uint64_t *counters, void *stream);
+int torj_trace_beams_plasmas(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                             const int *beam_plasma, const torj_trace_cfg *cfg, int n_beams,
+                             const int *beam_off, const double *omega, const int *mode,
+                             const double *x0, const double *N0, const double *weights, int n_psi,
+                             const double *psi_grid, const double *x_launch, const double *s0,
+                             double *state, int *status, int *steps, double *dP_shell,
+                             double *P_dep, double *traj);
+int torj_ray_entry_beams_plasmas_device(torj_plasma_t p, int n_plasmas,
+                                        const torj_plasma_t *plasmas, const int *beam_plasma,
+                                        int n_beams, const int *beam_off, const double *omega,
+                                        const int *mode, const double *x0, const double *N0,
+                                        double *x_plasma, double *N_plasma, double *s0,
+                                        int *status, void *stream);
+int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                                     const int *beam_plasma, int n_beams, const int *beam_off,
+                                     const double *omega, const int *mode, const double *x0,
+                                     const double *N0, double *x_plasma, double *N_plasma,
+                                     double *s0, int *status);
 
 /* make_beam's fan-out and reduce across the GPUs of this process
  * (src/solve.jl:209-240: one task per ray, then sum_i w_i dP_dV_i and

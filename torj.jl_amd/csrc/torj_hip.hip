@@ -9,6 +9,7 @@
 //   torj_k_depo.hpp     the reference-faithful deposition's kernels
 //   torj_k_points.hpp   ray entry and the batched point evaluations
 //   torj_k_beams.hpp    the multi-beam forms of k_trace and the kernels around it
+//   torj_k_beams_pl.hpp ... the same for beams that go through differing plasmas
 //   torj_host_util.hpp  fail / HIPCK, the environment knobs, GrowBuf
 //   torj_plasma.hpp     the plasma handle and its device state
 //   torj_fan.hpp        quadrature nodes and the launch fan
@@ -45,6 +46,7 @@ using namespace torj;
 #include "torj_k_depo.hpp"
 #include "torj_k_points.hpp"
 #include "torj_k_beams.hpp"
+#include "torj_k_beams_pl.hpp"
 #include "torj_plasma.hpp"
 #include "torj_fan.hpp"
 #include "torj_split.hpp"
@@ -571,19 +573,22 @@ int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, cons
                             steps, dP, Pdep, traj, counters, stream);
 }
 
-// ---- many beams of differing frequency and mode in one launch (beams_plan, torj_k_beams.hpp) ----
-int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
-                            const double *omega, const int *mode, const double *x0, const double *N0,
-                            const double *weights, int n_psi, const double *grid, const double *x_launch,
-                            const double *s0, double *state, int *status, int *steps, double *dP,
-                            double *Pdep, double *traj, uint64_t *counters, void *stream) {
+// ---- many beams of differing frequency and mode in one launch (beams_plan, torj_k_beams.hpp),
+// and through differing plasmas (`ps`: beams_plasmas_plan, torj_k_beams_pl.hpp) ----
+}  // extern "C"
+
+static int beams_device_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
+                              const int *beam_off, const double *omega, const int *mode, const double *x0,
+                              const double *N0, const double *weights, int n_psi, const double *grid,
+                              const double *x_launch, const double *s0, double *state, int *status, int *steps,
+                              double *dP, double *Pdep, double *traj, uint64_t *counters, void *stream) {
     if (!p || !cfg) return fail("bad plasma handle or cfg");
     if (!stream) {  // the NULL stream as the caller's: torj_trace_device_ex's fork and join
         // (argument errors first, without a device)
-        BeamsPlan bp;
+        BeamsPlasmasPlan pp;
         const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
                                 x_launch != nullptr, s0 != nullptr, traj != nullptr};
-        if (beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+        if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
         if (ensure_device(p)) return -1;
         if (!p->ev_Nin) {
             HIPCK(hipEventCreateWithFlags(&p->ev_Nin, hipEventDisableTiming));
@@ -591,29 +596,30 @@ int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_be
         }
         HIPCK(hipEventRecord(p->ev_Nin, nullptr));
         HIPCK(hipStreamWaitEvent(p->stream, p->ev_Nin, 0));
-        const int rc = torj_trace_beams_device(p, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid,
-                                               x_launch, s0, state, status, steps, dP, Pdep, traj, counters, p->stream);
+        const int rc = beams_device_entry(p, ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid,
+                                          x_launch, s0, state, status, steps, dP, Pdep, traj, counters, p->stream);
         HIPCK(hipEventRecord(p->ev_Nout, p->stream));
         HIPCK(hipStreamWaitEvent(nullptr, p->ev_Nout, 0));
         return rc;
     }
     if (p->timing) p->timing_calls++;
-    return beams_trace_device(p, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
+    return beams_trace_device(p, ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
                               state, status, steps, dP, Pdep, traj, counters, (hipStream_t)stream);
 }
 
-int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
-                     const double *omega, const int *mode, const double *x0, const double *N0,
-                     const double *weights, int n_psi, const double *grid, const double *x_launch,
-                     const double *s0, double *state, int *status, int *steps, double *dP, double *Pdep,
-                     double *traj) {
+// host pointers, synchronous, checked
+static int beams_host_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
+                            const int *beam_off, const double *omega, const int *mode, const double *x0,
+                            const double *N0, const double *weights, int n_psi, const double *grid,
+                            const double *x_launch, const double *s0, double *state, int *status, int *steps,
+                            double *dP, double *Pdep, double *traj) {
     if (!p || !cfg) return fail("bad plasma handle or cfg");
     const bool depo = n_psi >= 2 && grid;
     {  // argument errors before any device work (the device form repeats them on its pointers)
-        BeamsPlan bp;
+        BeamsPlasmasPlan pp;
         const LaunchPtrs has = {x0 && N0 && state && status && steps, depo, depo, x_launch != nullptr,
                                 s0 != nullptr, traj != nullptr};
-        if (beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+        if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
     }
     if (depo)
         for (int k = 1; k < n_psi; k++)
@@ -641,8 +647,8 @@ int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, co
     if (B.alloc(&dstate, 7 * (size_t)n, true) || B.alloc(&dstatus, n, true) || B.alloc(&dsteps, n, true) ||
         B.alloc(&dtraj, (size_t)n_save * 5 * n, traj && n_save > 0))
         return -1;
-    if (torj_trace_beams_device(p, cfg, n_beams, beam_off, omega, mode, dx0, dN0, dw, depo ? n_psi : 0, dgrid, dxl,
-                                ds0, dstate, dstatus, dsteps, ddP, dPdep, dtraj, nullptr, s))
+    if (beams_device_entry(p, ps, cfg, n_beams, beam_off, omega, mode, dx0, dN0, dw, depo ? n_psi : 0, dgrid, dxl,
+                           ds0, dstate, dstatus, dsteps, ddP, dPdep, dtraj, nullptr, s))
         return -1;
     if (ddownload(state, dstate, 7 * (size_t)n, s) || ddownload(status, dstatus, n, s) ||
         ddownload(steps, dsteps, n, s))
@@ -657,30 +663,53 @@ int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, co
     return torj_trace_check(p, s);
 }
 
-int torj_ray_entry_beams_device(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
-                                const int *mode, const double *x0, const double *N0, double *xp, double *Np,
-                                double *s0, int *status, void *stream) {
+// the ray entry's argument errors: the tables', then the arrays'; no HIP call
+static int entry_beams_check(torj_plasma_t p, const PlasmaSel *ps, int n_beams, const int *beam_off,
+                             const double *omega, const int *mode, const double *x0, const double *N0, double *xp,
+                             double *Np, double *s0, int *status) {
     if (!p) return fail("bad plasma handle");
+    if (ps && beams_plasmas_check(ps->n, (const void *const *)ps->list, ps->beam_plasma, p->device, kHandleView))
+        return -1;
     if (beams_tables_check(n_beams, beam_off, omega, mode)) return -1;
+    if (ps && beam_plasma_check(ps->n, ps->beam_plasma, n_beams)) return -1;
     if (!x0 || !N0 || !xp || !Np || !s0 || !status) return fail("x0, N0, x_plasma, N_plasma, s0, status required");
+    return 0;
+}
+
+static int entry_beams_device(torj_plasma_t p, const PlasmaSel *ps, int n_beams, const int *beam_off,
+                              const double *omega, const int *mode, const double *x0, const double *N0, double *xp,
+                              double *Np, double *s0, int *status, void *stream) {
+    if (entry_beams_check(p, ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status)) return -1;
     const int n = beam_off[n_beams];
     if (n == 0) return 0;
-    if (ensure_device(p)) return -1;
+    if (ensure_devices(p, ps)) return -1;
+    const dim3 grd(nblocks(n, 64)), blk(64);
     const BeamRec *d_beams;
-    if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, (hipStream_t)stream, &d_beams, nullptr))
-        return -1;
     EntryArgs a{p->d_coef, p->g, p->psi_prof_max, 0.0, 0, n, x0, N0, xp, Np, s0, status};
-    hipLaunchKernelGGL(k_ray_entry_beams, dim3(nblocks(n, 64)), dim3(64), 0, (hipStream_t)stream, a, d_beams, n_beams);
+    if (ps) {
+        BeamsPlasmasPlan pp;  // (the two tables the upload takes from it)
+        pp.beam_pl.assign(ps->beam_plasma, ps->beam_plasma + n_beams);
+        for (int j = 0; j < ps->n; j++) pp.plasmas.push_back(kHandleView.rec(ps->list[j]));
+        const PlasmaRec *d_plasmas;
+        const int *d_beam_pl;
+        if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, (hipStream_t)stream, &d_beams, nullptr,
+                         &pp, &d_plasmas, &d_beam_pl))
+            return -1;
+        hipLaunchKernelGGL(k_ray_entry_beams_pl, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams, d_plasmas,
+                           d_beam_pl);
+    } else {
+        if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, (hipStream_t)stream, &d_beams, nullptr))
+            return -1;
+        hipLaunchKernelGGL(k_ray_entry_beams, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams);
+    }
     HIPCK(hipGetLastError());
     return 0;
 }
 
-int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
-                             const int *mode, const double *x0, const double *N0, double *xp, double *Np,
-                             double *s0, int *status) {
-    if (!p) return fail("bad plasma handle");
-    if (beams_tables_check(n_beams, beam_off, omega, mode)) return -1;
-    if (!x0 || !N0 || !xp || !Np || !s0 || !status) return fail("x0, N0, x_plasma, N_plasma, s0, status required");
+static int entry_beams_host(torj_plasma_t p, const PlasmaSel *ps, int n_beams, const int *beam_off,
+                            const double *omega, const int *mode, const double *x0, const double *N0, double *xp,
+                            double *Np, double *s0, int *status) {
+    if (entry_beams_check(p, ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status)) return -1;
     const int n = beam_off[n_beams];
     if (n == 0) return 0;
     if (ensure_device(p)) return -1;
@@ -692,12 +721,83 @@ int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off, 
     if (B.alloc(&dxp, 3 * (size_t)n, true) || B.alloc(&dNp, 3 * (size_t)n, true) || B.alloc(&ds0, n, true) ||
         B.alloc(&dst, n, true))
         return -1;
-    if (torj_ray_entry_beams_device(p, n_beams, beam_off, omega, mode, dx0, dN0, dxp, dNp, ds0, dst, s)) return -1;
+    if (entry_beams_device(p, ps, n_beams, beam_off, omega, mode, dx0, dN0, dxp, dNp, ds0, dst, s)) return -1;
     if (ddownload(xp, dxp, 3 * (size_t)n, s) || ddownload(Np, dNp, 3 * (size_t)n, s) || ddownload(s0, ds0, n, s) ||
         ddownload(status, dst, n, s))
         return -1;
     HIPCK(hipStreamSynchronize(s));
     return 0;
+}
+
+extern "C" {
+
+int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+                            const double *omega, const int *mode, const double *x0, const double *N0,
+                            const double *weights, int n_psi, const double *grid, const double *x_launch,
+                            const double *s0, double *state, int *status, int *steps, double *dP,
+                            double *Pdep, double *traj, uint64_t *counters, void *stream) {
+    return beams_device_entry(p, nullptr, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch,
+                              s0, state, status, steps, dP, Pdep, traj, counters, stream);
+}
+
+int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+                     const double *omega, const int *mode, const double *x0, const double *N0,
+                     const double *weights, int n_psi, const double *grid, const double *x_launch,
+                     const double *s0, double *state, int *status, int *steps, double *dP, double *Pdep,
+                     double *traj) {
+    return beams_host_entry(p, nullptr, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch,
+                            s0, state, status, steps, dP, Pdep, traj);
+}
+
+int torj_ray_entry_beams_device(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
+                                const int *mode, const double *x0, const double *N0, double *xp, double *Np,
+                                double *s0, int *status, void *stream) {
+    return entry_beams_device(p, nullptr, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status, stream);
+}
+
+int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
+                             const int *mode, const double *x0, const double *N0, double *xp, double *Np,
+                             double *s0, int *status) {
+    return entry_beams_host(p, nullptr, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status);
+}
+
+// beam b through plasmas[beam_plasma[b]]; p is the launch's handle (stream, scratch, flags, knobs)
+int torj_trace_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                                    const int *beam_plasma, const torj_trace_cfg *cfg, int n_beams,
+                                    const int *beam_off, const double *omega, const int *mode, const double *x0,
+                                    const double *N0, const double *weights, int n_psi, const double *grid,
+                                    const double *x_launch, const double *s0, double *state, int *status,
+                                    int *steps, double *dP, double *Pdep, double *traj, uint64_t *counters,
+                                    void *stream) {
+    const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
+    return beams_device_entry(p, &ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
+                              state, status, steps, dP, Pdep, traj, counters, stream);
+}
+
+int torj_trace_beams_plasmas(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas, const int *beam_plasma,
+                             const torj_trace_cfg *cfg, int n_beams, const int *beam_off, const double *omega,
+                             const int *mode, const double *x0, const double *N0, const double *weights, int n_psi,
+                             const double *grid, const double *x_launch, const double *s0, double *state,
+                             int *status, int *steps, double *dP, double *Pdep, double *traj) {
+    const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
+    return beams_host_entry(p, &ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
+                            state, status, steps, dP, Pdep, traj);
+}
+
+int torj_ray_entry_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                                        const int *beam_plasma, int n_beams, const int *beam_off,
+                                        const double *omega, const int *mode, const double *x0, const double *N0,
+                                        double *xp, double *Np, double *s0, int *status, void *stream) {
+    const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
+    return entry_beams_device(p, &ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status, stream);
+}
+
+int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                                     const int *beam_plasma, int n_beams, const int *beam_off, const double *omega,
+                                     const int *mode, const double *x0, const double *N0, double *xp, double *Np,
+                                     double *s0, int *status) {
+    const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
+    return entry_beams_host(p, &ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status);
 }
 
 int torj_power_deposition_profile(torj_plasma_t p, int n_rays, const int *n_points, const double *s,

@@ -6,7 +6,8 @@
 // written once for the trace, torj_power_deposition_profile and the batch size;
 // trace_device_one enqueues what the plan says, one short launcher per path;
 // trace_batched is torj_trace_device_ex's loop over ray batches; beams_plan and
-// beams_trace_device are the same two steps for a multi-beam launch.  Also here,
+// beams_trace_device are the same two steps for a multi-beam launch, and
+// beams_plasmas_plan adds a plasma per beam to that plan.  Also here,
 // ahead of its first user: the Gauss-Legendre table's upload.
 // The planning comes first and needs no kernel header: TORJ_LAUNCH_PLAN_ONLY
 // stops there (the CPU test's harness).
@@ -14,6 +15,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "../../include/torj_hip.h"
@@ -268,11 +270,67 @@ static int beams_plan(BeamsPlan &bp, const torj_trace_cfg &cfg, int n_beams, con
     return 0;
 }
 
+// ---- BeamsPlasmasPlan: a multi-beam launch whose beams go through differing plasmas
+// (torj_trace_beams_plasmas_device): beam b through the listed plasma beam_plasma[b].
+// It is beams_plan's plan -- the wave table, the lanes per ray on the whole launch's
+// padded lanes, the workspace of all n rays -- plus the per-beam plasma index and one
+// record per listed plasma, in listed order (a plasma may be listed twice or unused).
+// The listed handles are opaque here: the caller says how to read one (PlasmaView).
+constexpr int kMaxPlasmas = 4096;
+
+struct PlasmaView {
+    int (*device)(const void *handle);
+    PlasmaRec (*rec)(const void *handle);  // device pointers: valid once the handle's device state exists
+};
+
+struct BeamsPlasmasPlan {
+    BeamsPlan bp;
+    std::vector<int> beam_pl;        // n_beams
+    std::vector<PlasmaRec> plasmas;  // n_plasmas
+};
+
+// the two host tables the plasma form adds, checked; `device` is the launching handle's
+static int beams_plasmas_check(int n_plasmas, const void *const *plasmas, const int *beam_plasma, int device,
+                               const PlasmaView &view) {
+    if (n_plasmas < 1 || n_plasmas > kMaxPlasmas) return fail("n_plasmas must be 1..%d", kMaxPlasmas);
+    if (!plasmas) return fail("plasmas is NULL");
+    if (!beam_plasma) return fail("beam_plasma is NULL");
+    for (int j = 0; j < n_plasmas; j++)
+        if (!plasmas[j]) return fail("plasmas[%d] is NULL", j);
+    for (int j = 0; j < n_plasmas; j++)
+        if (view.device(plasmas[j]) != device)
+            return fail("plasmas[%d] is on device %d, the launching handle on device %d (one device per launch)", j,
+                        view.device(plasmas[j]), device);
+    return 0;
+}
+// (after beams_tables_check: n_beams is within its range)
+static int beam_plasma_check(int n_plasmas, const int *beam_plasma, int n_beams) {
+    for (int b = 0; b < n_beams; b++)
+        if (beam_plasma[b] < 0 || beam_plasma[b] >= n_plasmas)
+            return fail("beam_plasma[%d] = %d is outside 0..%d (n_plasmas = %d)", b, beam_plasma[b], n_plasmas - 1,
+                        n_plasmas);
+    return 0;
+}
+
+static int beams_plasmas_plan(BeamsPlasmasPlan &pp, const torj_trace_cfg &cfg, int n_plasmas,
+                              const void *const *plasmas, const int *beam_plasma, int device, const PlasmaView &view,
+                              int n_beams, const int *beam_off, const double *omega, const int *mode, int n_psi,
+                              const LaunchPtrs &has, const LaunchKnobs &kn) {
+    if (beams_plasmas_check(n_plasmas, plasmas, beam_plasma, device, view)) return -1;
+    if (beams_plan(pp.bp, cfg, n_beams, beam_off, omega, mode, n_psi, has, kn)) return -1;
+    if (beam_plasma_check(n_plasmas, beam_plasma, n_beams)) return -1;
+    pp.beam_pl.assign(beam_plasma, beam_plasma + n_beams);
+    pp.plasmas.resize(n_plasmas);
+    for (int j = 0; j < n_plasmas; j++) pp.plasmas[j] = view.rec(plasmas[j]);
+    return 0;
+}
+
 #ifndef TORJ_LAUNCH_PLAN_ONLY
 #include <mutex>
 
 #include "torj_dispatch.hpp"
 #include "torj_k_beams.hpp"
+#include "torj_k_beams_pl.hpp"
 #include "torj_k_fused.hpp"
 #include "torj_k_points.hpp"
 #include "torj_split.hpp"
@@ -477,15 +535,63 @@ static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, c
 // returns; the buffer is the handle's scratch (one stream per handle), so a launch
 // enqueued earlier on `s` has read its own tables before these arrive.
 static int beams_upload(torj_plasma_s *p, const std::vector<BeamRec> &beams, const std::vector<BeamWave> &waves,
-                        hipStream_t s, const BeamRec **d_beams, const BeamWave **d_waves) {
+                        hipStream_t s, const BeamRec **d_beams, const BeamWave **d_waves,
+                        const BeamsPlasmasPlan *pp = nullptr, const PlasmaRec **d_plasmas = nullptr,
+                        const int **d_beam_pl = nullptr) {
+    // (every table's size is a multiple of 8 bytes but the last's, so each starts aligned)
     const size_t nb = beams.size() * sizeof(BeamRec), nw = waves.size() * sizeof(BeamWave);
-    if (ensure_buf(p, p->beams, nb + nw)) return -1;
+    const size_t np = pp ? pp->plasmas.size() * sizeof(PlasmaRec) : 0, ni = pp ? pp->beam_pl.size() * sizeof(int) : 0;
+    if (ensure_buf(p, p->beams, nb + nw + np + ni)) return -1;
     char *d = (char *)p->beams.d;
-    HIPCK(hipMemcpyAsync(d, beams.data(), nb, hipMemcpyHostToDevice, s));
-    if (nw) HIPCK(hipMemcpyAsync(d + nb, waves.data(), nw, hipMemcpyHostToDevice, s));
     *d_beams = (const BeamRec *)d;
     if (d_waves) *d_waves = (const BeamWave *)(d + nb);
+    if (pp) {  // a launch through several plasmas: their records and the beams' indices behind the two,
+        // all four tables packed and sent as one copy
+        std::vector<char> h(nb + nw + np + ni);
+        if (nb) memcpy(h.data(), beams.data(), nb);
+        if (nw) memcpy(h.data() + nb, waves.data(), nw);
+        memcpy(h.data() + nb + nw, pp->plasmas.data(), np);
+        if (ni) memcpy(h.data() + nb + nw + np, pp->beam_pl.data(), ni);
+        HIPCK(hipMemcpyAsync(d, h.data(), h.size(), hipMemcpyHostToDevice, s));
+        *d_plasmas = (const PlasmaRec *)(d + nb + nw);
+        *d_beam_pl = (const int *)(d + nb + nw + np);
+        return 0;
+    }
+    HIPCK(hipMemcpyAsync(d, beams.data(), nb, hipMemcpyHostToDevice, s));
+    if (nw) HIPCK(hipMemcpyAsync(d + nb, waves.data(), nw, hipMemcpyHostToDevice, s));
     return 0;
+}
+
+// ---- the plasmas of a launch through several (torj_trace_beams_plasmas_device): the
+// caller's two host tables; a null PlasmaSel is the launching handle's own plasma ----
+struct PlasmaSel {
+    int n;
+    const torj_plasma_t *list;
+    const int *beam_plasma;
+};
+static const PlasmaView kHandleView = {
+    [](const void *h) { return ((const torj_plasma_s *)h)->device; },
+    [](const void *h) {
+        const torj_plasma_s *q = (const torj_plasma_s *)h;
+        return PlasmaRec{q->d_coef, q->d_cellp, q->g, q->psi_prof_max};
+    }};
+
+// beams_plan, or beams_plasmas_plan when plasmas are given: argument errors, no HIP call
+static int beams_any_plan(BeamsPlasmasPlan &pp, const torj_plasma_s *p, const PlasmaSel *ps, const torj_trace_cfg &cfg,
+                          int n_beams, const int *beam_off, const double *omega, const int *mode, int n_psi,
+                          const LaunchPtrs &has) {
+    if (!ps) return beams_plan(pp.bp, cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p));
+    return beams_plasmas_plan(pp, cfg, ps->n, (const void *const *)ps->list, ps->beam_plasma, p->device, kHandleView,
+                              n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p));
+}
+
+// the device state of every listed handle, then the launching one's (created on a
+// handle's first GPU use: d_coef is null before).  All are on p's device (checked).
+static int ensure_devices(torj_plasma_s *p, const PlasmaSel *ps) {
+    if (ps)
+        for (int j = 0; j < ps->n; j++)
+            if (ensure_device(ps->list[j])) return -1;
+    return ensure_device(p);
 }
 
 // k_trace_beams' instance: k_trace's set (launch_lanes)
@@ -500,21 +606,37 @@ static void launch_beams(const BeamsArgs &ba, const BeamsPlan &bp, hipStream_t s
             if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace_beams<A(), D(), T()>), grd, blk, 0, s, ba);
         });
 }
+// k_trace_beams_pl's: the same set
+static void launch_beams_pl(const BeamsPlArgs &pa, const BeamsPlan &bp, hipStream_t s) {
+    const dim3 grd((unsigned)bp.waves.size()), blk(64);
+    if (bp.lpr == 16)
+        with_depo_traj(bp.DM, bp.tr, [&](auto D, auto T) {
+            if constexpr (D() != kDepoBinned)
+                hipLaunchKernelGGL((k_trace_beams_pl<1, D(), T(), 16>), grd, blk, 0, s, pa);
+        });
+    else
+        with_abs_depo_traj(pa.b.a.abs_model == 1 ? 1 : 0, bp.DM, bp.tr, [&](auto A, auto D, auto T) {
+            if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace_beams_pl<A(), D(), T()>), grd, blk, 0, s, pa);
+        });
+}
 
-// one multi-beam launch on stream `s` (the body of torj_trace_beams_device); the
-// three host tables are consumed before it returns
-static int beams_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
+// one multi-beam launch on stream `s` (the body of torj_trace_beams_device and, with
+// `ps`, of torj_trace_beams_plasmas_device); the host tables are consumed before it returns
+static int beams_trace_device(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
+                              const int *beam_off,
                               const double *omega, const int *mode, const double *x0, const double *N0,
                               const double *weights, int n_psi, const double *grid, const double *x_launch,
                               const double *s0, double *state, int *status, int *steps, double *dP,
                               double *Pdep, double *traj, uint64_t *counters, hipStream_t s) {
     const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
                             x_launch != nullptr, s0 != nullptr, traj != nullptr};
-    BeamsPlan bp;
+    BeamsPlasmasPlan pp;
+    const BeamsPlan &bp = pp.bp;
     const bool fresh = !p->d_flags;  // n_cu is the device's only once ensure_device has run
-    if (beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
-    if (ensure_device(p)) return -1;
-    if (fresh && beams_plan(bp, *cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p))) return -1;
+    if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
+    if (ensure_devices(p, ps)) return -1;
+    // (again with plasmas: their records hold device pointers, which exist only now)
+    if ((fresh || ps) && beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
     const int n = bp.n;
     if (n == 0) return 0;
     if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
@@ -525,12 +647,15 @@ static int beams_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_
                         "the budget of %zu bytes (TORJ_WS_GB); trace the beams in separate calls",
                         n, bp.lay.bytes(), budget);
     }
-    BeamsArgs ba{};
+    BeamsPlArgs pa{};
+    BeamsArgs &ba = pa.b;
     torj_trace_cfg c1 = *cfg;  // (omega and mode are the beams'; any valid pair here)
     c1.omega = omega[0], c1.mode = mode[0];
+    // (with plasmas a.coef, a.cellp and a.g are p's and unused: the beam's plasma record gives them)
     TraceArgs &a = ba.a = trace_args(p, c1, n, x0, N0, weights, s0, state, status, steps, counters);
     ba.n_beams = n_beams;
-    if (beams_upload(p, bp.beams, bp.waves, s, &ba.beams, &ba.waves)) return -1;
+    if (beams_upload(p, bp.beams, bp.waves, s, &ba.beams, &ba.waves, ps ? &pp : nullptr, &pa.plasmas, &pa.beam_pl))
+        return -1;
     if (bp.depo) {
         a.n_psi = n_psi, a.grid = grid, a.dP = dP;
         if (!Pdep) {
@@ -554,15 +679,27 @@ static int beams_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_
     if (bp.fit && fit_zero(fa, s)) return -1;
     hipEvent_t ev[3];
     if (timing_begin(p, ev, s)) return -1;
-    launch_beams(ba, bp, s);
+    if (ps)
+        launch_beams_pl(pa, bp, s);
+    else
+        launch_beams(ba, bp, s);
     HIPCK(hipGetLastError());
     if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
     if (bp.fit) {  // launch_post with the beams' kernels
         const dim3 grd(nblocks(n, 64)), blk(64);
         with_abs(a.abs_model, [&](auto A) {
-            if constexpr (A() <= 1) hipLaunchKernelGGL(k_final_alpha_beams<A()>, grd, blk, 0, s, ba);
+            if constexpr (A() <= 1) {
+                if (ps)
+                    hipLaunchKernelGGL(k_final_alpha_beams_pl<A()>, grd, blk, 0, s, pa);
+                else
+                    hipLaunchKernelGGL(k_final_alpha_beams<A()>, grd, blk, 0, s, ba);
+            }
         });
-        hipLaunchKernelGGL(k_fit_depo, grd, blk, fit_grid_lds(fa.n_psi), s, fa);
+        if (ps)
+            hipLaunchKernelGGL(k_fit_depo_pl, grd, blk, fit_grid_lds(fa.n_psi), s, fa, ba.beams, n_beams, pa.plasmas,
+                               pa.beam_pl);
+        else
+            hipLaunchKernelGGL(k_fit_depo, grd, blk, fit_grid_lds(fa.n_psi), s, fa);
         hipLaunchKernelGGL(k_shell_sum_beams, dim3(fa.n_psi, n_beams), dim3(256), 0, s, fa, ba.beams);
         HIPCK(hipGetLastError());
     }

@@ -314,10 +314,15 @@ end
 """make_beams(plasma, launchers, s_max, psi_dP_dV; ...) -- one make_beam tuple per launcher,
 every launcher's rays in ONE launch.  `launchers`: tuples (r, phi, z, tor, pol, spot, inv_curv,
 f, mode), make_beam's leading arguments."""
-function make_beams(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{Float64};
-                    ds::Float64=1e-4, N_rings::Integer=3, min_azimuthal_points::Integer=5,
-                    normalize_weight_sum::Bool=true, deposition::Integer=1, absorption::Integer=1,
-                    traj_stride::Integer=1)
+make_beams(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{Float64}; kw...) =
+    _make_beams(p, nothing, nothing, launchers, s_max, psi_dP_dV; kw...)
+
+# the body of both make_beams methods: `plasmas === nothing` is the launching plasma for every beam
+function _make_beams(p::GPUPlasma, plasmas, beam_plasma, launchers, s_max::Float64,
+                     psi_dP_dV::Vector{Float64};
+                     ds::Float64=1e-4, N_rings::Integer=3, min_azimuthal_points::Integer=5,
+                     normalize_weight_sum::Bool=true, deposition::Integer=1, absorption::Integer=1,
+                     traj_stride::Integer=1)
     traj_stride >= 1 || throw(ArgumentError("traj_stride must be >= 1"))
     B = length(launchers)
     beam_off, omega, mode = zeros(Cint, B + 1), zeros(B), zeros(Cint, B)
@@ -331,7 +336,8 @@ function make_beams(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{F
         omega[b], mode[b] = 2π * f, m
     end
     pos, dirs, w = vcat((a[1] for a in fans)...), vcat((a[2] for a in fans)...), vcat((a[3] for a in fans)...)
-    xp, Np, s0, st = ray_entry_beams(p, beam_off, omega, mode, pos, dirs)
+    sel = plasmas === nothing ? () : (plasmas, Cint.(beam_plasma .- 1))  # the C tables count from 0
+    xp, Np, s0, st = ray_entry_beams(p, sel..., beam_off, omega, mode, pos, dirs)
     for b in 1:B
         bad = count(st[beam_off[b]+1:beam_off[b+1]] .!= 0)
         bad == 0 || throw(AssertionError("beam $b: ray entry failed for $bad rays"))
@@ -339,13 +345,14 @@ function make_beams(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{F
     n_steps = max(1, round(Int, s_max / ds))
     cfg = TraceCfg(omega[1], mode[1], ds, n_steps, max(1, n_steps ÷ 100), 1.0, 1e-6, absorption,
                    traj_stride, deposition, 0, 1e-6, 1e-6, s_max, 100)
-    state, status, steps, dP, Pdep, traj = trace_beams(p, cfg, beam_off, omega, mode, xp, Np, w,
+    state, status, steps, dP, Pdep, traj = trace_beams(p, sel..., cfg, beam_off, omega, mode, xp, Np, w,
                                                         psi_dP_dV, pos, s0)
-    dV = shell_volumes(p, psi_dP_dV)
+    # the shells' volumes: the launching plasma's, or each listed plasma's own
+    dV = plasmas === nothing ? [shell_volumes(p, psi_dP_dV)] : [shell_volumes(q, psi_dP_dV) for q in plasmas]
     out = []
     for b in 1:B
         dP_dV = zeros(length(psi_dP_dV))
-        dP_dV[1:end-1] .= dP[1:end-2, b] ./ dV
+        dP_dV[1:end-1] .= dP[1:end-2, b] ./ dV[plasmas === nothing ? 1 : beam_plasma[b]]
         arc_lengths, trajectories, ray_powers = Vector{Vector{Float64}}(), Vector{Vector{Vector{Float64}}}(), Vector{Vector{Float64}}()
         for i in beam_off[b]+1:beam_off[b+1]
             k = steps[i] ÷ traj_stride
@@ -362,6 +369,100 @@ function make_beams(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{F
     return out
 end
 make_beams(p::TorJ.Plasma, args...; kw...) = make_beams(gpu_plasma(p), args...; kw...)
+
+# ---- ... through differing plasmas (torj_trace_beams_plasmas) ----
+# beam b goes through plasmas[beam_plasma[b]]; p is the launching handle (stream, scratch, knobs),
+# listed or not; every listed plasma is on p's device.  The C tables count plasmas from 0.
+_handles(plasmas::Vector{GPUPlasma}) = Ptr{Cvoid}[q.h for q in plasmas]
+
+function ray_entry_beams(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma0::Vector{Cint},
+                         beam_off::Vector{Cint}, omega::Vector{Float64}, mode::Vector{Cint},
+                         x0::Matrix{Float64}, N0::Matrix{Float64})
+    n = size(x0, 1)
+    hs = _handles(plasmas)
+    xp, Np, s0, st = zeros(n, 3), zeros(n, 3), zeros(n), zeros(Cint, n)
+    GC.@preserve plasmas hs begin
+        check(ccall((:torj_ray_entry_beams_plasmas_gpu, libtorj), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                    p.h, length(hs), hs, beam_plasma0, length(omega), beam_off, omega, mode, x0, N0, xp, Np,
+                    s0, st))
+    end
+    return xp, Np, s0, st
+end
+
+function trace_beams(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma0::Vector{Cint}, cfg::TraceCfg,
+                     beam_off::Vector{Cint}, omega::Vector{Float64}, mode::Vector{Cint},
+                     x0::Matrix{Float64}, N0::Matrix{Float64}, w::Vector{Float64},
+                     psi_grid::Vector{Float64}, x_launch::Matrix{Float64}, s0::Vector{Float64})
+    n, B = size(x0, 1), length(omega)
+    hs = _handles(plasmas)
+    n_save = cfg.traj_stride > 0 ? cfg.n_steps ÷ cfg.traj_stride : 0
+    state, status, steps = zeros(n, 7), zeros(Cint, n), zeros(Cint, n)
+    dP, Pdep = zeros(length(psi_grid) + 1, B), zeros(n)
+    traj = n_save > 0 ? zeros(n, 5, n_save) : zeros(0, 5, 0)
+    GC.@preserve plasmas hs beam_plasma0 beam_off omega mode x0 N0 w psi_grid x_launch s0 begin
+        check(ccall((:torj_trace_beams_plasmas, libtorj), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Ref{TraceCfg}, Cint, Ptr{Cint}, Ptr{Float64},
+                     Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    p.h, length(hs), hs, beam_plasma0, cfg, B, beam_off, omega, mode, x0, N0, w,
+                    length(psi_grid), psi_grid, x_launch, s0, state, status, steps, dP, Pdep,
+                    n_save > 0 ? traj : C_NULL))
+    end
+    return state, status, steps, dP, Pdep, traj
+end
+
+# the device forms: every array but the five host tables is device memory (Ptr{Cvoid}), the call is
+# enqueued on `stream`; torj_trace_check(p, stream) follows the last of them
+function ray_entry_beams_device(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma0::Vector{Cint},
+                                beam_off::Vector{Cint}, omega::Vector{Float64}, mode::Vector{Cint},
+                                x0::Ptr{Cvoid}, N0::Ptr{Cvoid}, xp::Ptr{Cvoid}, Np::Ptr{Cvoid},
+                                s0::Ptr{Cvoid}, status::Ptr{Cvoid}, stream::Ptr{Cvoid})
+    hs = _handles(plasmas)
+    GC.@preserve plasmas hs begin
+        check(ccall((:torj_ray_entry_beams_plasmas_device, libtorj), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint},
+                     Ptr{Cvoid}),
+                    p.h, length(hs), hs, beam_plasma0, length(omega), beam_off, omega, mode,
+                    Ptr{Float64}(x0), Ptr{Float64}(N0), Ptr{Float64}(xp), Ptr{Float64}(Np), Ptr{Float64}(s0),
+                    Ptr{Cint}(status), stream))
+    end
+    return nothing
+end
+
+function trace_beams_device(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma0::Vector{Cint},
+                            cfg::TraceCfg, beam_off::Vector{Cint}, omega::Vector{Float64},
+                            mode::Vector{Cint}, x0::Ptr{Cvoid}, N0::Ptr{Cvoid}, w::Ptr{Cvoid}, n_psi::Integer,
+                            psi_grid::Ptr{Cvoid}, x_launch::Ptr{Cvoid}, s0::Ptr{Cvoid}, state::Ptr{Cvoid},
+                            status::Ptr{Cvoid}, steps::Ptr{Cvoid}, dP::Ptr{Cvoid}, Pdep::Ptr{Cvoid},
+                            traj::Ptr{Cvoid}, counters::Ptr{Cvoid}, stream::Ptr{Cvoid})
+    hs = _handles(plasmas)
+    GC.@preserve plasmas hs begin
+        check(ccall((:torj_trace_beams_plasmas_device, libtorj), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Ref{TraceCfg}, Cint, Ptr{Cint}, Ptr{Float64},
+                     Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{UInt64}, Ptr{Cvoid}),
+                    p.h, length(hs), hs, beam_plasma0, cfg, length(omega), beam_off, omega, mode,
+                    Ptr{Float64}(x0), Ptr{Float64}(N0), Ptr{Float64}(w), n_psi, Ptr{Float64}(psi_grid),
+                    Ptr{Float64}(x_launch), Ptr{Float64}(s0), Ptr{Float64}(state), Ptr{Cint}(status),
+                    Ptr{Cint}(steps), Ptr{Float64}(dP), Ptr{Float64}(Pdep), Ptr{Float64}(traj),
+                    Ptr{UInt64}(counters), stream))
+    end
+    return nothing
+end
+
+"""make_beams(p, plasmas, beam_plasma, launchers, s_max, psi_dP_dV; ...) -- launcher b through
+plasmas[beam_plasma[b]] (indices from 1), all in ONE launch on p's device; tuple b equals
+make_beam's on that plasma, dP_dV taken with that plasma's shell volumes."""
+function make_beams(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma::Vector{<:Integer}, launchers,
+                    s_max::Float64, psi_dP_dV::Vector{Float64}; kw...)
+    length(beam_plasma) == length(launchers) || throw(ArgumentError("beam_plasma needs one entry per launcher"))
+    all(1 .<= beam_plasma .<= length(plasmas)) || throw(ArgumentError("beam_plasma must index plasmas (from 1)"))
+    return _make_beams(p, plasmas, beam_plasma, launchers, s_max, psi_dP_dV; kw...)
+end
 
 """alpha(...) of src/general_absorption.jl:1328-1337 (repaired, DESIGN.md §3.6) at n
 points on the GPU: iwarm 1 (weakly) or 3 (fully relativistic); inv_dDdN = 1/|dD/dN|.

@@ -20,6 +20,7 @@ CSRC = os.path.join(_ROOT, "csrc")
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _u64p = C.POINTER(C.c_uint64)
+_hp = C.POINTER(C.c_void_p)  # const torj_plasma_t *
 
 
 class TorjError(RuntimeError):
@@ -110,6 +111,17 @@ _SIGS = {
     "torj_ray_entry_beams_device": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _ip] + [C.c_void_p] * 7),
     "torj_ray_entry_beams_gpu": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _ip, _dp, _dp, _dp, _dp, _dp,
                                            _ip]),
+    # ... through differing plasmas: plasmas (handles) and beam_plasma are host tables too
+    "torj_trace_beams_plasmas_device": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.POINTER(TraceCfg), C.c_int,
+                                                  _ip, _dp, _ip] + [C.c_void_p] * 3 + [C.c_int] +
+                                        [C.c_void_p] * 11),
+    "torj_trace_beams_plasmas": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.POINTER(TraceCfg), C.c_int, _ip, _dp,
+                                           _ip, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp,
+                                           _dp]),
+    "torj_ray_entry_beams_plasmas_device": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.c_int, _ip, _dp, _ip] +
+                                            [C.c_void_p] * 7),
+    "torj_ray_entry_beams_plasmas_gpu": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.c_int, _ip, _dp, _ip, _dp,
+                                                   _dp, _dp, _dp, _dp, _ip]),
     "torj_shell_volumes": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "torj_power_deposition_profile": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp,
                                                 _dp, _dp]),
@@ -156,6 +168,13 @@ def dptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(_ip) if a is not None else None
+
+
+def handles(plasmas):
+    """Plasma objects (None: a NULL entry) -> the C array of their handles, or None"""
+    if plasmas is None:
+        return None
+    return (C.c_void_p * len(plasmas))(*[None if q is None else q.handle for q in plasmas])
 
 
 def f64(a):

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import TraceCfg, TorjError, check, dptr, f64, iptr, lib, soa
+from ._lib import TraceCfg, TorjError, check, dptr, f64, handles, iptr, lib, soa
 from .launch import launch_peripheral_rays, pol_tor_angles_2_vector
 
 OK, LEFT_PLASMA, ABSORBED, NAN, REFLECTED, ENTRY_FAIL, MAX_STEPS = range(7)
@@ -141,10 +141,27 @@ def _beam_tables(beam_off, omega, mode):
     return off, om, md
 
 
-def ray_entry_beams(plasma, beam_off, omega, mode, x0, N0):
+def _plasma_tables(plasmas, beam_plasma, n_beams):
+    """The two further host tables of a call through several plasmas: the listed
+    handles and beam b's index into them (both or neither)."""
+    if plasmas is None and beam_plasma is None:
+        return None
+    if plasmas is None or beam_plasma is None:
+        raise ValueError("plasmas and beam_plasma go together")
+    bp = np.ascontiguousarray(beam_plasma, dtype=np.int32)
+    if bp.ndim != 1 or len(bp) != n_beams:
+        raise ValueError("beam_plasma needs n_beams entries")
+    return len(plasmas), handles(plasmas), iptr(bp), bp
+
+
+def ray_entry_beams(plasma, beam_off, omega, mode, x0, N0, *, plasmas=None, beam_plasma=None):
     """ray_entry(..., gpu=True) for the concatenated rays of several beams, ray i
-    with its beam's omega and mode, in one launch (torj_ray_entry_beams_gpu)."""
+    with its beam's omega and mode, in one launch (torj_ray_entry_beams_gpu).
+    With plasmas (a sequence of Plasma) and beam_plasma (n_beams indices into it)
+    beam b enters plasmas[beam_plasma[b]], with that plasma's own psi_prof_max
+    (torj_ray_entry_beams_plasmas_gpu); `plasma` is then the launching handle."""
     off, om, md = _beam_tables(beam_off, omega, mode)
+    pt = _plasma_tables(plasmas, beam_plasma, len(om))
     xs, Ns = soa(x0), soa(N0)
     n = xs.shape[1]
     if len(off) and off[-1] != n:
@@ -152,22 +169,33 @@ def ray_entry_beams(plasma, beam_off, omega, mode, x0, N0):
     xp, Np = np.zeros((3, n)), np.zeros((3, n))
     s0 = np.zeros(n)
     st = np.zeros(n, dtype=np.int32)
-    check(lib().torj_ray_entry_beams_gpu(plasma.handle, len(om), iptr(off), dptr(om), iptr(md), dptr(xs),
-                                         dptr(Ns), dptr(xp), dptr(Np), dptr(s0), iptr(st)))
+    args = (len(om), iptr(off), dptr(om), iptr(md), dptr(xs), dptr(Ns), dptr(xp), dptr(Np), dptr(s0), iptr(st))
+    if pt is None:
+        check(lib().torj_ray_entry_beams_gpu(plasma.handle, *args))
+    else:
+        check(lib().torj_ray_entry_beams_plasmas_gpu(plasma.handle, *pt[:3], *args))
     return xp.T.copy(), Np.T.copy(), s0, st
 
 
 def trace_beams(plasma, beam_off, omega, mode, x0, N0, *, ds: float = 1e-4, n_steps: int,
                 chunk_steps: int | None = None, psi_exit: float = 1.0, P_min: float = 1e-6,
                 absorption=True, psi_grid=None, weights=None, traj_stride: int = 0,
-                deposition: str = "binned", x_launch=None, s0=None) -> TraceResult:
+                deposition: str = "binned", x_launch=None, s0=None, plasmas=None,
+                beam_plasma=None) -> TraceResult:
     """trace() for the concatenated rays of several beams in ONE launch
     (torj_trace_beams): beam b owns rays beam_off[b] .. beam_off[b + 1] - 1 and
     is traced with omega[b] and mode[b]; every other setting is shared.
     dP_shell has shape (n_beams, n_psi + 1), row b beam b's.  Fixed-step RK4 with
     absorption "none" or "albajar" only; per-ray results equal trace()'s on each
-    beam alone."""
+    beam alone.
+
+    plasmas (a sequence of Plasma on `plasma`'s device) and beam_plasma (n_beams
+    indices into it): beam b is traced through plasmas[beam_plasma[b]]
+    (torj_trace_beams_plasmas) and its results equal trace()'s on that plasma;
+    `plasma` is then the launching handle (its set_sched knobs, stream and scratch),
+    listed or not.  The grids of the plasmas may differ."""
     off, om, md = _beam_tables(beam_off, omega, mode)
+    pt = _plasma_tables(plasmas, beam_plasma, len(om))
     xs, Ns = soa(x0), soa(N0)
     n = xs.shape[1]
     if len(off) and off[-1] != n:
@@ -188,9 +216,13 @@ def trace_beams(plasma, beam_off, omega, mode, x0, N0, *, ds: float = 1e-4, n_st
     Pdep = np.zeros(n)
     n_save = n_steps // traj_stride if traj_stride > 0 else 0
     traj = np.zeros((n_save, 5, n)) if n_save > 0 else None
-    check(lib().torj_trace_beams(plasma.handle, cfg, len(om), iptr(off), dptr(om), iptr(md), dptr(xs),
-                                 dptr(Ns), dptr(w), n_psi, dptr(g) if n_psi else None, dptr(xl), dptr(sv),
-                                 dptr(state), iptr(status), iptr(steps), dptr(dP), dptr(Pdep), dptr(traj)))
+    args = (cfg, len(om), iptr(off), dptr(om), iptr(md), dptr(xs), dptr(Ns), dptr(w), n_psi,
+            dptr(g) if n_psi else None, dptr(xl), dptr(sv), dptr(state), iptr(status), iptr(steps), dptr(dP),
+            dptr(Pdep), dptr(traj))
+    if pt is None:
+        check(lib().torj_trace_beams(plasma.handle, *args))
+    else:
+        check(lib().torj_trace_beams_plasmas(plasma.handle, *pt[:3], *args))
     return TraceResult(state.T.copy(), status, steps, dP, Pdep,
                        traj.transpose(2, 0, 1).copy() if traj is not None else None)
 
@@ -305,14 +337,16 @@ def make_beam(plasma, r: float, phi: float, z: float, steering_angle_tor: float,
 
 
 def make_beams(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, traj_stride: int = 1,
-               deposition: str = "reference", absorption="albajar", **kwargs):
+               deposition: str = "reference", absorption="albajar", plasmas=None, beam_plasma=None, **kwargs):
     """make_beam for several launchers in ONE launch (torj_ray_entry_beams_gpu,
     torj_trace_beams): `launchers` is a sequence of (r, phi, z, steering_angle_tor,
     steering_angle_pol, spot_size, inverse_curvature_radius, f, mode), make_beam's
     leading arguments; returns one make_beam tuple per launcher, equal to what
     make_beam gives for it.  Fixed-step RK4, absorption "albajar" or "none";
     kwargs go to launch_peripheral_rays.  Raises RayEntryError naming the beam
-    when a ray fails entry."""
+    when a ray fails entry.  With plasmas and beam_plasma (see trace_beams)
+    launcher b goes through plasmas[beam_plasma[b]] and its tuple equals
+    make_beam's on that plasma, dP_dV taken with that plasma's shell volumes."""
     fans, omega, mode, off = [], [], [], [0]
     for (r, phi, z, tor, pol, spot, inv_curv, f, m) in launchers:
         N0 = pol_tor_angles_2_vector(pol, tor)
@@ -322,7 +356,8 @@ def make_beams(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, 
         mode.append(int(m))
         off.append(off[-1] + len(fans[-1][2]))
     pos, dirs, w = (np.concatenate([fan[k] for fan in fans]) for k in range(3))
-    xp, Np, s0, st = ray_entry_beams(plasma, off, omega, mode, pos, dirs)
+    sel = dict(plasmas=plasmas, beam_plasma=beam_plasma)
+    xp, Np, s0, st = ray_entry_beams(plasma, off, omega, mode, pos, dirs, **sel)
     for b in range(len(fans)):
         bad = np.flatnonzero(st[off[b]:off[b + 1]] != OK)
         if len(bad):
@@ -331,12 +366,13 @@ def make_beams(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, 
     g = f64(psi_dP_dV)
     res = trace_beams(plasma, off, omega, mode, xp, Np, ds=ds, n_steps=_steps_for(s_max, ds), psi_grid=g,
                       weights=w, traj_stride=traj_stride, deposition=deposition, x_launch=pos, s0=s0,
-                      absorption=absorption)
-    dV = plasma.shell_volumes(g)
+                      absorption=absorption, **sel)
+    # the shells' volumes: the launching plasma's, or each listed plasma's own
+    dV = [q.shell_volumes(g) for q in plasmas] if plasmas is not None else [plasma.shell_volumes(g)]
     out = []
     for b in range(len(fans)):
         dP_dV = np.zeros(len(g))
-        dP_dV[:-1] = res.dP_shell[b, :len(g) - 1] / dV
+        dP_dV[:-1] = res.dP_shell[b, :len(g) - 1] / dV[beam_plasma[b] if plasmas is not None else 0]
         lists = _ray_lists(res, range(off[b], off[b + 1]), pos, xp, s0, ds, traj_stride)
         out.append((*lists, dP_dV, float(res.dP_shell[b, len(g)]), w[off[b]:off[b + 1]]))
     return out
