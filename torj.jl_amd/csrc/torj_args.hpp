@@ -72,6 +72,9 @@ constexpr int kDepoNone = 0, kDepoBinned = 1, kDepoSamples = 2;
 #define TORJ_WARM_MIN_WAVES 1
 #endif
 
+// alpha-input buffers in flight in the split pipeline (the ring: torj_split.hpp)
+constexpr int kSplitRing = 4;
+
 constexpr int kAinF = 5;  // X, Y, |N|^2, N_par, ln Te (warm: X, Y, |N|, N_par, Te, 1 / |dD/dN|: kAinFW)
 constexpr int kAinFW = 6;
 
@@ -93,6 +96,10 @@ struct SplitArgs {
                            // stage point the trajectory kernel stored (zero_box_flag); null: off
     double zval;           // what a fully flagged alpha wave writes: 0, or NaN under the test hook
                            // TORJ_TEST_ZFLAG_NAN=1 (the flagged waves then stop their rays NAN)
+    unsigned *gflag;       // per 64-ray group, this block (ring slot): 1 = every ray of the group carries
+                           // zflag 1.  Written once per wave by the trajectory kernel; the group's alpha
+                           // waves end on it and the scan takes zval for the group's alphas (nothing is
+                           // stored for them).  Null: off (TORJ_ALPHA_GFLAG=0, or zflag null)
     int k0, kb;           // block: steps [k0, k0 + kb)
     int nf;               // alpha input fields per point: kAinF (Albajar) or kAinFW (warm)
     int tile_cap;         // k_traj_tile: most nodes a wave stages (<= kTileNodes)
@@ -108,6 +115,20 @@ struct SplitArgs {
                                 // environment turns it off).  In the struct's tail padding: the kernels'
                                 // arguments after a SplitArgs keep their offsets
 };
+
+// Word g of SplitArgs::gflag for the wave's own group (g wave-uniform), read
+// through the constant address space so that it is a scalar load, issued without
+// a vector-memory round trip.  Only for a word that an earlier kernel wrote and
+// no kernel running now writes (the scalar cache is not coherent with vector
+// stores): the readers say why that holds.
+__device__ __forceinline__ unsigned group_word(const unsigned *gflag, int g) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) unsigned *const_ptr;
+    return ((const_ptr)(unsigned long long)gflag)[g];
+#else
+    return gflag[g];
+#endif
+}
 
 // steps | status << 24: split launches need n_steps < kSplitMaxSteps (the
 // fused kernels have no such limit and take longer traces)

@@ -24,6 +24,38 @@
 // trace phase, 128: 45.6-45.7, 64: 46.7-48.6 alternating)
 #endif
 constexpr int kAlphaBlock = TORJ_ALPHA_BLOCK;
+static_assert(kAlphaBlock % 64 == 0, "an alpha wave holds one 64-ray group");
+// The head of an alpha wave (round 13).  Before: five dependent round trips
+// ahead of the first fp64 instruction -- a.n; the tinfo / sinfo / zflag
+// pointers; ti, si and the flag byte, waited for because the wave's exit hangs on
+// the byte; the ain / alpha pointers and nf; the five inputs.  Now: the kernel
+// arguments in one scalar batch (alpha_args_batch), the group's flag word as one
+// scalar load (alpha_group_flagged), and for a wave that evaluates, ti, si and
+// the five inputs as one vector batch behind a single wait.
+//
+// every kernel argument the head needs, consumed by an empty asm so that the
+// compiler loads them together at the top instead of each before its first use
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TORJ_ALPHA_ARGS_BATCH(a, sp)                                                                        \
+    asm volatile("" ::"s"((a).n), "s"((sp).gflag), "s"((sp).zflag), "s"((sp).tinfo), "s"((sp).sinfo),      \
+                 "s"((sp).ain), "s"((sp).alpha), "s"((sp).nf), "s"((sp).k0))
+#else
+#define TORJ_ALPHA_ARGS_BATCH(a, sp) \
+    do {                             \
+    } while (0)
+#endif
+// The word of the wave's 64-ray group (SplitArgs::gflag; w0: the wave's first
+// ray, wave-uniform and < n).  Uniform address, so a scalar load, and a scalar
+// load is safe here: the word was written by the trajectory kernel of this
+// block, which finished before this kernel was launched (the stream event
+// between them), and it sits in a 256-byte-aligned array of its ring slot alone,
+// which no kernel running beside this one writes -- the trajectory kernels ahead
+// write other slots' arrays, never this line, until this block's scan is done.
+// So the scalar cache, which is not coherent with vector stores, cannot hold an
+// older copy than the launch's own invalidate leaves it.
+__device__ __forceinline__ bool alpha_group_flagged(const SplitArgs &sp, int w0) {
+    return sp.gflag != nullptr && group_word(sp.gflag, w0 >> 6) != 0u;
+}
 #ifndef TORJ_ALPHA_SETPRIO
 #define TORJ_ALPHA_SETPRIO 0
 #endif
@@ -34,18 +66,43 @@ __global__ void __launch_bounds__(kAlphaBlock, TORJ_ALPHA_WAVES) k_alpha_pts(Tra
 #endif
     const int q = blockIdx.x, js = blockIdx.y;  // js = j * 4 + stage (a 2-D grid: no division)
     const int i = q * kAlphaBlock + threadIdx.x;
+    TORJ_ALPHA_ARGS_BATCH(a, sp);
+    const int w0 = __builtin_amdgcn_readfirstlane(i & ~63);  // the wave's first ray
+    if (w0 >= a.n) return;  // a whole wave past the last ray (it has no group word)
+    // a group whose rays all carry the trajectory kernel's block zero flag
+    // (abs_albajar_fast_body's early settle returns +0 at every point of theirs):
+    // the wave ends here, with no vector load and no store -- the scan reads the
+    // same word and takes sp.zval for the group's alphas, 0 for its work words
+    // (39 % of the headline beam's waves; round 6 ended them behind one vector
+    // round trip and 512 B of zeros each)
+    if (alpha_group_flagged(sp, w0)) {
+#if defined(TORJ_ALPHA_PROF) && defined(__HIP_DEVICE_COMPILE__)
+        TORJ_APROF_WAVE(kAprofZ);
+#endif
+        return;
+    }
     if (i >= a.n) return;
     const int j = js >> 2;
-    // the stop words and the block's zero flag first
+    // the stop words and the five inputs at once (one memory latency; the
+    // addresses are valid for any i < n whether or not the point is live).  The
+    // per-ray flag byte rides with them only where it is looked at: without
+    // group words (TORJ_ALPHA_GFLAG=0), or for the TORJ_ALPHA_PROF census
+#if defined(TORJ_ALPHA_PROF)
+    const bool want_zf = sp.zflag != nullptr;
+#else
+    const bool want_zf = sp.zflag != nullptr && sp.gflag == nullptr;
+#endif
     const int ti = sp.tinfo[i], si = sp.sinfo[i];
-    const int zf = sp.zflag ? sp.zflag[i] : 0;
-    // the trajectory kernel's block zero flags: a wave whose rays all carry one
-    // writes 0 (abs_albajar_fast_body's early settle returns +0 there) and ends
-    // before its input loads are issued (round 6: waiting for the five inputs
-    // too, as below, cost the flagged 39 % of the waves a memory latency and
-    // ~12 GB of reads per launch; C3 trace -1.2 ms alternating,
-    // profiles/r06/ab_log.txt r6zff)
-    if (__all(zf != 0)) {
+    const int zf = want_zf ? sp.zflag[i] : 0;
+    const double *in = sp.ain + (size_t)js * sp.nf * a.n + i;
+    const double X = in[0], Y = in[(size_t)a.n], N2 = in[2 * (size_t)a.n], Npar = in[3 * (size_t)a.n];
+    const double lnTe = in[4 * (size_t)a.n];
+    // (an empty asm that consumes them: the compiler would otherwise sink the
+    // input loads below the stop test and the Te test, three latencies in a row)
+    asm volatile("" ::"v"(ti), "v"(si), "v"(zf), "v"(X), "v"(Y), "v"(N2), "v"(Npar), "v"(lnTe));
+    // without group words: a wave whose rays all carry the flag writes the zeros
+    // itself, as since round 6 (now behind the one batch, inputs included)
+    if (sp.gflag == nullptr && __all(zf != 0)) {
 #if defined(TORJ_ALPHA_PROF) && defined(__HIP_DEVICE_COMPILE__)
         TORJ_APROF_WAVE(kAprofZ);
 #endif
@@ -53,14 +110,6 @@ __global__ void __launch_bounds__(kAlphaBlock, TORJ_ALPHA_WAVES) k_alpha_pts(Tra
         if constexpr (COUNT) sp.awork[(size_t)js * a.n + i] = 0u;
         return;
     }
-    // the five inputs at once (one memory latency, not three in a row; their
-    // addresses are valid for any i < n whether or not the point is live)
-    const double *in = sp.ain + (size_t)js * sp.nf * a.n + i;
-    const double X = in[0], Y = in[(size_t)a.n], N2 = in[2 * (size_t)a.n], Npar = in[3 * (size_t)a.n];
-    const double lnTe = in[4 * (size_t)a.n];
-    // (an empty asm that consumes them: the compiler would otherwise sink the
-    // input loads below the stop test and the Te test, three latencies in a row)
-    asm volatile("" ::"v"(ti), "v"(si), "v"(X), "v"(Y), "v"(N2), "v"(Npar), "v"(lnTe));
     // sinfo may be stale (k_tau_scan of an earlier block runs on another
     // stream): an optimisation only, as in traj_body -- a stale OK evaluates an
     // alpha the scan never reads
@@ -106,6 +155,11 @@ __global__ void __launch_bounds__(kAlphaBlock, TORJ_ALPHA_WAVES) k_alpha_pts(Tra
 template <bool COUNT, int P>
 __global__ void __launch_bounds__(kAlphaBlock, TORJ_ALPHA_WAVES) k_alpha_pts_mp(TraceArgs a, SplitArgs sp, int nq) {
     const int i = blockIdx.x * kAlphaBlock + threadIdx.x;
+    TORJ_ALPHA_ARGS_BATCH(a, sp);
+    const int w0 = __builtin_amdgcn_readfirstlane(i & ~63);  // the wave's first ray
+    if (w0 >= a.n) return;
+    // a flagged group (as k_alpha_pts): none of the block's points is evaluated or stored
+    if (alpha_group_flagged(sp, w0)) return;
     if (i >= a.n) return;
     const int js0 = blockIdx.y * P;
     const int np = min(P, 4 * sp.kb - js0);  // workgroup-uniform

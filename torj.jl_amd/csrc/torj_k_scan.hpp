@@ -46,19 +46,29 @@ __device__ __forceinline__ void tau_scan_body(const TraceArgs &a, const SplitArg
     // counters [2..7] (include/torj_hip.h): Albajar or warm iwarm 1 meanings
     unsigned long long nsteps = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0;
     const int am = a.abs_model;
+    // the group's flag word (SplitArgs::gflag; the workgroup is the group, so a
+    // scalar load, safe as in k_alpha_pts): a flagged group's alpha waves stored
+    // nothing -- its alphas are sp.zval and its work words 0, taken from here
+    const bool gz = sp.gflag != nullptr && group_word(sp.gflag, (int)blockIdx.x) != 0u;
     if (i < a.n) {
         int steps = 0, st = ST_OK;
         double tau = 0.0, psi_a = 0.0, Pdep = 0.0;
+        // the carry's loads issued together, the trajectory's stop word with them
+        // (it used to wait behind sinfo's status): one memory latency, not two
+        int sv = 0;
+        const int tv = sp.tinfo[i];  // packed: steps and status written together
         if (sp.k0 > 0) {
-            const int v = sp.sinfo[i];
-            steps = info_steps(v);
-            st = info_status(v);
+            sv = sp.sinfo[i];
             tau = sp.stau[i];
             Pdep = sp.sPdep[i];
         }
         if constexpr (DEPO == kDepoBinned) psi_a = sp.spsi[i];
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" ::"v"(tv), "v"(sv), "v"(tau), "v"(Pdep), "v"(psi_a));
+#endif
+        steps = info_steps(sv);
+        st = info_status(sv);
         if (st == ST_OK) {
-            const int tv = sp.tinfo[i];  // packed: steps and status written together
             const int tT = info_steps(tv), tS = info_status(tv);
             const double w = (DEPO == kDepoBinned && a.w) ? a.w[i] : 1.0;
             const double ds6 = a.ds / 6.0;
@@ -76,7 +86,7 @@ __device__ __forceinline__ void tau_scan_body(const TraceArgs &a, const SplitArg
                 for (int v = 0; v < kScanBatch; v++) {
                     const size_t ov = (size_t)(min(sb + v, s_end - 1) - sp.k0) * 4 * a.n + i;
 #pragma unroll
-                    for (int q = 0; q < 4; q++) alb[v][q] = sp.alpha[ov + q * (size_t)a.n];
+                    for (int q = 0; q < 4; q++) alb[v][q] = gz ? sp.zval : sp.alpha[ov + q * (size_t)a.n];
                 }
 #pragma unroll
                 for (int v = 0; v < kScanBatch; v++) {
@@ -102,7 +112,7 @@ __device__ __forceinline__ void tau_scan_body(const TraceArgs &a, const SplitArg
                     }
 #pragma unroll
                     for (int q = 0; q < 4 && COUNT; q++) {
-                        const unsigned wk = sp.awork[o + q * (size_t)a.n];
+                        const unsigned wk = gz ? 0u : sp.awork[o + q * (size_t)a.n];
                         if (am == 1) {
                             c2 += wk & 1u;
                             c3 += (wk >> 1) & 3u;

@@ -322,7 +322,16 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
         sp.tx[(3 + c) * (size_t)a.n + i] = N[c];
     }
     sp.tinfo[i] = make_info(steps, st);
-    if (sp.zflag != nullptr) sp.zflag[i] = zero_box_flag(zb) ? 1 : 0;
+    if (sp.zflag != nullptr) {
+        const bool zf = zero_box_flag(zb);
+        sp.zflag[i] = zf ? 1 : 0;
+        // the group's word (SplitArgs::gflag): the lanes here are the wave's rays
+        // with steps in this block, reconverged behind the step loop; a lane that
+        // left in traj_body carries flag 1 by definition, so the `all` over these
+        // is the group's.  Every one of them stores the same word to the same
+        // address: the wave's one store, whichever lanes are left
+        if (sp.gflag != nullptr) sp.gflag[i >> 6] = __all(zf) ? 1u : 0u;
+    }
 }
 
 
@@ -362,6 +371,12 @@ __device__ __forceinline__ void traj_body(const TraceArgs &a, const SplitArgs &s
         // a ray without trajectory steps in this block needs no alpha in it
         if (!live && sp.zflag) sp.zflag[i] = 1;
     }
+    // A wave without a live ray never reaches traj_run's store of the group's
+    // word: it writes the 1 here, in every mode (the tile kernels return
+    // wave-uniformly below, the others lane by lane).  The ring slot still holds
+    // the word of kRing blocks ago, so a skipped write is a wrong flag, not a
+    // missing one.  (i < n: a wave past the last group has no word)
+    if (sp.gflag != nullptr && !__any(live) && i < a.n) sp.gflag[i >> 6] = 1u;
     if constexpr (MODE == kTrajTile) {
         // one wave per workgroup: the wave's live rays' (R, Z) box, widened by
         // the path the block can take, and its nodes staged in LDS
@@ -393,7 +408,7 @@ __device__ __forceinline__ void traj_body(const TraceArgs &a, const SplitArgs &s
     } else if constexpr (MODE == kTrajCell) {
         // the cells the wave's live rays can reach in the block (the node tile's
         // box, by cell), their power-form records staged in LDS
-        __shared__ __attribute__((aligned(16))) double s_cell[kTileCells * kCellRec];
+        __shared__ __attribute__((aligned(16))) double s_cell[kTileCells * kCellLds];
         const double R = sqrt(x[0] * x[0] + x[1] * x[1]);
         const double inf = __builtin_inf();
         const double rmin = wave_min(live ? R : inf), rmax = wave_max(live ? R : -inf);
@@ -419,7 +434,7 @@ __device__ __forceinline__ void traj_body(const TraceArgs &a, const SplitArgs &s
             for (int zr = 0; zr < ch; zr++)
                 for (int rr = 0; rr < cw; rr++)
                     if (threadIdx.x < kCellRec / 2)
-                        dst[(zr * cw + rr) * (kCellRec / 2) + threadIdx.x] =
+                        dst[(zr * cw + rr) * (kCellLds / 2) + threadIdx.x] =
                             src[((size_t)(cZ0 + zr) * cR + cR0 + rr) * (kCellRec / 2) + threadIdx.x];
         }
         __syncthreads();

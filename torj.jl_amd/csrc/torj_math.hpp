@@ -519,6 +519,16 @@ TORJ_HD void fields_finish_d(const Grid &g, double dRx, double dZx, const double
 // by ulps (x, N ~1e-15 after 2 000 steps, tests/test_gpu_split.py).
 constexpr int kCellNS = 6;
 constexpr int kCellRec = kCellNS * 16;
+// A cell's record in the trajectory kernel's LDS tile (k_traj_cell): kCellRec
+// doubles are 768 B = 3 x 64 dwords, so the same coefficient of any two cells
+// sits in the same LDS bank, and a 16-lane group of a ds_read_b128 whose lanes
+// are in K cells takes K passes.  TORJ_CELL_LDS_PAD=1 stages the records 98
+// doubles apart (784 B, still 16-byte aligned): consecutive cells one 16-byte
+// bank slot apart; the values read are the same.  0 (the default): 96.
+#ifndef TORJ_CELL_LDS_PAD
+#define TORJ_CELL_LDS_PAD 0
+#endif
+constexpr int kCellLds = kCellRec + (TORJ_CELL_LDS_PAD ? 2 : 0);
 struct CellAxis {
     int i;
     double t, delta;  // t: the offset from the cell's corner in metres
@@ -649,7 +659,7 @@ TORJ_HD void eval_fields(const TileCell &t, const Grid &g, const CellAxis &aR, c
 #pragma unroll
     for (int f = 0; f < NT; f++) gr[f] = gz[f] = grz[f] = 0.0;
     if (in)
-        cell_sums<NGRAD, NVAL, EXT, LdsP>((LdsP)t.lds + (size_t)(dZ * t.cw + dR) * kCellRec, aR, aZ, fidx, v,
+        cell_sums<NGRAD, NVAL, EXT, LdsP>((LdsP)t.lds + (size_t)(dZ * t.cw + dR) * kCellLds, aR, aZ, fidx, v,
                                           gr, gz, grz);
     else
         cell_sums<NGRAD, NVAL, EXT, GlbP>((GlbP)t.g + ((size_t)aZ.i * (g.nR - 1) + aR.i) * kCellRec, aR, aZ,

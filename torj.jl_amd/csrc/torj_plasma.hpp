@@ -10,6 +10,7 @@
 #include <mutex>
 #include <vector>
 
+#include "torj_args.hpp"
 #include "torj_host_util.hpp"
 #include "torj_math.hpp"
 
@@ -176,7 +177,7 @@ struct torj_plasma_s {
     hipStream_t stream2 = nullptr, streamT = nullptr;  // alpha; trajectory (high priority)
     hipStream_t streamS = nullptr;                      // optical-depth scan
     hipStream_t streamD = nullptr;                      // streamed deposition windows (TORJ_DEPO_STREAM=2)
-    static constexpr int kRing = 4;                     // alpha-input buffers in flight
+    static constexpr int kRing = kSplitRing;                  // alpha-input buffers in flight
     hipEvent_t ev_T[kRing] = {}, ev_A[kRing] = {}, ev_S[kRing] = {}, ev_J = nullptr, ev_F = nullptr;
     hipEvent_t ev_D = nullptr;
     hipEvent_t ev_Nin = nullptr, ev_Nout = nullptr;  // a NULL caller stream's fork / join

@@ -2,9 +2,18 @@
 // call (SplitPlan), the carving of the handle's ring workspace, and the block
 // loop with its streams and events (split_trace).
 // (a slice of torj_hip.hip / torj_traj.hip: included after `using namespace torj`)
+//
+// The plan's sizes and the carving come first and need no kernel header and no
+// HIP call: TORJ_SPLIT_PLAN_ONLY stops the file after them, for a host build
+// (tests/native/split_plan_host.hip).
 #pragma once
+#include <algorithm>
 #include <atomic>
 
+#include "torj_args.hpp"
+#include "torj_fitdepo.hpp"
+#include "torj_host_util.hpp"
+#ifndef TORJ_SPLIT_PLAN_ONLY
 #include "torj_dispatch.hpp"
 #include "torj_k_alpha.hpp"
 #include "torj_k_depo.hpp"
@@ -25,17 +34,18 @@ static int fit_zero(const FitArgs &fa, hipStream_t st) {
     HIPCK(hipMemsetAsync(fa.dPs, 0, L * N * sizeof(double), st));
     return 0;
 }
+#endif  // TORJ_SPLIT_PLAN_ONLY
 
 // What one split_trace call launches, fixed before anything is enqueued: the
 // blocks, the workspace's byte sizes, and the knobs' values read for this call.
 struct SplitPlan {
-    static constexpr int R = torj_plasma_s::kRing;
+    static constexpr int R = kSplitRing;
     size_t n;
     int n_steps, nf;
     long kb, first;  // steps per block; the first block's steps (0: uniform blocks)
     int n_blk;
-    size_t b_ain, b_alpha, b_awork, b_psib, b_cbx, b_n8, b_n4, b_zf, b_dsd, b_dsi, b_defer, b_dcnt, bytes;
-    bool zflag_on, dstream, serial;
+    size_t b_ain, b_alpha, b_awork, b_psib, b_cbx, b_n8, b_n4, b_zf, b_gf, b_dsd, b_dsi, b_defer, b_dcnt, bytes;
+    bool zflag_on, gflag_on, dstream, serial;
     int dstream_env, depo_lag, lds_env, tile_cap, nan_step, zflag_nan_from, defer_lrm, zlatch;
     double tile_margin;
 
@@ -48,9 +58,10 @@ struct SplitPlan {
 };
 
 // walk: the reference profile's walk can be streamed behind the scans (fa and dso given);
-// negl_skip: the Gauss-Legendre table's early settle is on (GLTable::negl_skip)
-static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a, int DM, bool walk,
-                      bool negl_skip) {
+// negl_skip: the Gauss-Legendre table's early settle is on (GLTable::negl_skip);
+// sched_mode, sched_waves: the handle's torj_set_sched; free_b: the device memory free now
+static void split_plan_sizes(SplitPlan &pl, int sched_mode, int sched_waves, size_t free_b, const TraceArgs &a,
+                             int DM, bool walk, bool negl_skip) {
     const size_t n = pl.n = (size_t)a.n;
     const int n_steps = pl.n_steps = a.n_steps;
     // steps per block: kRing alpha-input buffers within the budget (TORJ_SPLIT_MB
@@ -59,15 +70,13 @@ static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a,
     static const size_t budget_env = (size_t)env_long("TORJ_SPLIT_MB", 1024) << 20;
     // ... and at most 1/16 of the device memory free now for each of the kRing
     // buffers (a quarter of it for the whole ring; 1 GiB on an idle MI355X)
-    size_t free_b = 0, total_b = 0;
-    HIPCK(hipMemGetInfo(&free_b, &total_b));
     const size_t budget = std::max<size_t>(std::min(budget_env, free_b / 16), 1);
     pl.nf = a.abs_model >= 2 ? kAinFW : kAinF;
     const size_t per_step = 4 * (size_t)pl.nf * sizeof(double) * n;
     long kb = (long)std::max<size_t>(1, budget / per_step);
     kb = std::min<long>(kb, 16383);  // the alpha kernels' grid.y = 4 kb stays <= 65535
     if (a.chunk_steps > 0 && kb >= a.chunk_steps) kb -= kb % a.chunk_steps;
-    if (p->sched_mode == 3 && p->sched_waves > 0) kb = std::min(p->sched_waves, 16383);  // torj_set_sched(p, 3, steps per block)
+    if (sched_mode == 3 && sched_waves > 0) kb = std::min(sched_waves, 16383);  // torj_set_sched(p, 3, steps per block)
     kb = pl.kb = std::min<long>(kb, n_steps);
     const int n_cb = (a.chunk_steps > 0 ? n_steps / a.chunk_steps : 0) + 1;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -84,6 +93,12 @@ static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a,
     // TORJ_ALPHA_ZFLAG=0 (read per call) turns them off
     pl.zflag_on = a.abs_model == 1 && negl_skip && env_int("TORJ_ALPHA_ZFLAG", 1) != 0;
     pl.b_zf = pl.zflag_on ? al(n) : 0;
+    // the group flag words, one per 64-ray group and ring slot (SplitArgs::gflag):
+    // with the block zero flags unless TORJ_ALPHA_GFLAG=0 (read per call), which
+    // restores the per-ray test in k_alpha_pts, its zero stores and the scan's loads.
+    // Each slot's array is a multiple of 256 B, so no two slots share a cache line
+    pl.gflag_on = pl.zflag_on && env_int("TORJ_ALPHA_GFLAG", 1) != 0;
+    pl.b_gf = pl.gflag_on ? al(sizeof(unsigned) * ((n + 63) / 64)) : 0;
     // TORJ_ZBOX_LATCH=0 (read per call): the trajectory kernel keeps growing every
     // ray's box to the end of the block (traj_run's latch; the flags are the same)
     pl.zlatch = env_int("TORJ_ZBOX_LATCH", 1) != 0;
@@ -113,11 +128,11 @@ static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a,
     pl.b_defer = a.abs_model >= 2 ? al(4 * sizeof(unsigned long long) * n * kb) : 0;
     pl.b_dcnt = a.abs_model >= 2 ? al(sizeof(unsigned) * pl.n_blk) : 0;
     pl.bytes = pl.R * (pl.b_ain + pl.b_alpha + pl.b_awork) + pl.R * pl.b_psib + pl.b_cbx + 6 * pl.b_n8 +
-               3 * pl.b_n8 + 2 * pl.b_n4 + pl.b_dsd + pl.b_dsi + pl.b_defer + pl.b_dcnt + pl.R * pl.b_zf;
+               3 * pl.b_n8 + 2 * pl.b_n4 + pl.b_dsd + pl.b_dsi + pl.b_defer + pl.b_dcnt + pl.R * pl.b_zf + pl.R * pl.b_gf;
     // TORJ_SPLIT_SERIAL=1: every kernel on the caller's stream, no overlap (a
     // measurement aid; read per call so a test can compare both orders)
     pl.serial = env_int("TORJ_SPLIT_SERIAL", 0) != 0;
-    pl.depo_lag = std::min(torj_plasma_s::kRing - 1, std::max(1, env_int("TORJ_DEPO_LAG", 2)));
+    pl.depo_lag = std::min(kSplitRing - 1, std::max(1, env_int("TORJ_DEPO_LAG", 2)));
     // the trajectory kernel with the coefficients staged in LDS whenever the grid
     // fits 160 KiB at 6 fp64 per node (56 x 56: 161 KB), one workgroup of wpb
     // waves per CU (measured: trajectory kernel 28.2 -> 24.3 ms, pipeline 67.2 ->
@@ -151,7 +166,6 @@ static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a,
                             "waves write NaN\n");
     }
     pl.defer_lrm = std::min(3, std::max(0, env_int("TORJ_WARM_DEFER_LRM", 3)));
-    return 0;
 }
 
 // the ring slots and single arrays carved out of the handle's split workspace
@@ -160,6 +174,7 @@ struct SplitRing {
     double *ain[R], *alphas[R], *psib[R];
     unsigned *aworks[R];
     unsigned char *zflags[R];
+    unsigned *gflags[R];
     unsigned *dcnt;
     DepoStream ds;
 };
@@ -183,6 +198,8 @@ static void split_carve(const SplitPlan &pl, char *q, SplitArgs &sp, SplitRing &
         for (int r = 0; r < R; r++) rg.psib[r] = (double *)take(pl.b_psib);
     if (pl.b_zf)
         for (int r = 0; r < R; r++) rg.zflags[r] = (unsigned char *)take(pl.b_zf);
+    if (pl.b_gf)
+        for (int r = 0; r < R; r++) rg.gflags[r] = (unsigned *)take(pl.b_gf);
     sp.cbx = (double *)take(pl.b_cbx);
     sp.tx = (double *)take(6 * pl.b_n8);
     sp.stau = (double *)take(pl.b_n8);
@@ -196,6 +213,15 @@ static void split_carve(const SplitPlan &pl, char *q, SplitArgs &sp, SplitRing &
         rg.ds.d = (double *)take(pl.b_dsd);
         rg.ds.v = (int *)take(pl.b_dsi);
     }
+}
+
+#ifndef TORJ_SPLIT_PLAN_ONLY
+static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a, int DM, bool walk,
+                      bool negl_skip) {
+    size_t free_b = 0, total_b = 0;
+    HIPCK(hipMemGetInfo(&free_b, &total_b));
+    split_plan_sizes(pl, p->sched_mode, p->sched_waves, free_b, a, DM, walk, negl_skip);
+    return 0;
 }
 
 // The split RK4 path's launches: per block of kb steps, the
@@ -279,6 +305,7 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
         sp.ain = rg.ain[r];
         sp.psib = rg.psib[r];
         sp.zflag = rg.zflags[r];
+        sp.gflag = rg.gflags[r];  // null when the group words are off
         sp.zval = (pl.zflag_nan_from >= 0 && sp.k0 >= pl.zflag_nan_from) ? NAN : 0.0;
         sp.alpha = rg.alphas[r];
         sp.awork = pl.b_awork ? rg.aworks[r] : nullptr;  // work words only for a counted launch
@@ -382,3 +409,4 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
     HIPCK(hipGetLastError());
     return 0;
 }
+#endif  // TORJ_SPLIT_PLAN_ONLY
