@@ -335,6 +335,81 @@ def test_beams_plasmas_device_back_to_back(gpu, T, pl, beams):
     assert tot[0] == sum(int(r[2].sum()) for r in want) and tot[1] == 4 * tot[0]
 
 
+def test_null_stream_equals_explicit_stream(gpu, T, pl, beams):
+    """The three device-pointer traces with stream = 0 against the same call on a stream
+    of the caller's: the NULL stream's fork onto the handle's stream and the join back.
+    Beams 2, 3 and 4 of the fixture (5, 0 and 1 rays) through [P2, P1]; 1 200 steps, the
+    reference deposition on 20 boundaries, trajectory samples every 600 steps.  After the
+    stream-0 call the outputs are read by plain default-stream copies, with no
+    synchronize on the handle's stream: only the join orders them after the trace."""
+    import torch
+
+    hs, _ = pl
+    b = beams
+    dev = torch.device("cuda", 0)
+    L = T.lib()
+    lo, hi = 2, 5
+    sl = slice(b["off"][lo], b["off"][hi])
+    n, nb, n5 = sl.stop - sl.start, hi - lo, b["off"][lo + 1] - b["off"][lo]
+    assert (n, n5, BP[lo:hi]) == (6, 5, [2, 1, 2])
+    off = np.array(b["off"][lo:hi + 1], dtype=np.int32) - b["off"][lo]
+    om, md = np.array(b["omega"][lo:hi]), np.array(b["mode"][lo:hi], dtype=np.int32)
+    handles = (ctypes.c_void_p * 2)(hs[2].handle.value, hs[1].handle.value)
+    bpl = np.array([0, 1, 0], dtype=np.int32)
+    grid = np.linspace(0.0, 1.0, 20)
+    n_steps, stride = 1200, 600
+    n_save = n_steps // stride
+
+    def t(a, dtype=torch.float64):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev, dtype=dtype)
+
+    x0, N0, w = t(b["xp"][sl].T), t(b["Np"][sl].T), t(b["w"][sl])
+    xl, s0, g = t(b["pos"][sl].T), t(b["s0"][sl]), t(grid)
+    x5, N5, xl5 = t(b["xp"][sl][:n5].T), t(b["Np"][sl][:n5].T), t(b["pos"][sl][:n5].T)
+
+    def run(which, stream):
+        """one call on `stream` (0: the NULL stream); the outputs, read on torch's current stream"""
+        m, rows = (n5, 1) if which == "single" else (n, nb)
+        state = torch.zeros((7, m), dtype=torch.float64, device=dev)
+        status = torch.zeros(m, dtype=torch.int32, device=dev)
+        steps = torch.zeros(m, dtype=torch.int32, device=dev)
+        dP = torch.zeros((rows, len(grid) + 1), dtype=torch.float64, device=dev)
+        Pdep = torch.zeros(m, dtype=torch.float64, device=dev)
+        traj = torch.zeros((n_save, 5, m), dtype=torch.float64, device=dev)
+        out = (state, status, steps, dP, Pdep, traj)
+        tail = [len(grid), g.data_ptr()]
+        if which == "single":
+            cfg = T._lib.TraceCfg(om[0], int(md[0]), DS, n_steps, CHUNK, 1.0, 1e-6, 1, stride, 1)
+            tail += [xl5.data_ptr(), s0.data_ptr()] + [a.data_ptr() for a in out] + [None, stream]
+            rc = L.torj_trace_device_ex(hs[2].handle, cfg, n5, x5.data_ptr(), N5.data_ptr(), w.data_ptr(), *tail)
+        else:
+            cfg = T._lib.TraceCfg(0.0, 0, DS, n_steps, CHUNK, 1.0, 1e-6, 1, stride, 1)
+            tabs = (cfg, nb, T._lib.iptr(off), T._lib.dptr(om), T._lib.iptr(md), x0.data_ptr(), N0.data_ptr(),
+                    w.data_ptr())
+            tail += [xl.data_ptr(), s0.data_ptr()] + [a.data_ptr() for a in out] + [None, stream]
+            if which == "beams":
+                rc = L.torj_trace_beams_device(hs[2].handle, *tabs, *tail)
+            else:
+                rc = L.torj_trace_beams_plasmas_device(hs[2].handle, 2, handles, T._lib.iptr(bpl), *tabs, *tail)
+        T._lib.check(rc)
+        got = [a.cpu().numpy() for a in out]
+        assert L.torj_trace_check(hs[2].handle, stream) == 0
+        return got
+
+    side = torch.cuda.Stream(dev)
+    assert side.cuda_stream != 0
+    for which in ("single", "beams", "plasmas"):
+        null = run(which, 0)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            assert torch.cuda.current_stream(dev).cuda_stream == side.cuda_stream
+            own = run(which, side.cuda_stream)
+        side.synchronize()
+        for a, r in zip(null, own):
+            assert np.array_equal(a, r, equal_nan=a.dtype.kind == "f")
+        assert (null[2] > 0).all(), which  # every ray stepped
+
+
 def test_ray_entry_beams_plasmas_equals_per_beam(gpu, T, pl):
     """ray_entry_beams(plasmas=) against ray_entry(gpu=True) on each beam's plasma: the
     seven beams' fans and an eighth whose third ray points away from the plasma (not OK)."""

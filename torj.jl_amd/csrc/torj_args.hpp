@@ -188,7 +188,7 @@ struct BeamsArgs {
     int n_beams;
 };
 
-// ---- a multi-beam launch through several plasmas (torj_k_beams_pl.hpp; planned by
+// ---- a multi-beam launch through several plasmas (torj_k_beams.hpp; planned by
 // torj_launch.hpp beams_plasmas_plan) ----
 // one listed plasma: what TraceArgs (coef, cellp, g) and the ray entry (psi_max) take from a handle
 struct PlasmaRec {
@@ -199,8 +199,7 @@ struct PlasmaRec {
 };
 // BeamsArgs (a.coef, a.cellp, a.g unused: the beam's plasma gives them) and two more
 // device-resident tables: the listed plasmas' records, and beam b's index into them
-struct BeamsPlArgs {
-    BeamsArgs b;
+struct BeamsPlArgs : BeamsArgs {
     const PlasmaRec *plasmas;
     const int *beam_pl;  // n_beams
 };

@@ -8,8 +8,8 @@
 //   torj_k_scan.hpp     ... its optical-depth scan and final assembly
 //   torj_k_depo.hpp     the reference-faithful deposition's kernels
 //   torj_k_points.hpp   ray entry and the batched point evaluations
-//   torj_k_beams.hpp    the multi-beam forms of k_trace and the kernels around it
-//   torj_k_beams_pl.hpp ... the same for beams that go through differing plasmas
+//   torj_k_beams.hpp    the multi-beam forms of k_trace and the kernels around it,
+//                       also for beams that go through differing plasmas
 //   torj_host_util.hpp  fail / HIPCK, the environment knobs, GrowBuf
 //   torj_plasma.hpp     the plasma handle and its device state
 //   torj_fan.hpp        quadrature nodes and the launch fan
@@ -46,12 +46,85 @@ using namespace torj;
 #include "torj_k_depo.hpp"
 #include "torj_k_points.hpp"
 #include "torj_k_beams.hpp"
-#include "torj_k_beams_pl.hpp"
 #include "torj_plasma.hpp"
 #include "torj_fan.hpp"
 #include "torj_split.hpp"
 #include "torj_launch.hpp"
 #include "torj_beam.hpp"
+
+// ===========================================================================
+// host-pointer entries: the arrays staged around a device-pointer call
+// ===========================================================================
+// a host copy of psi_dP_dV, checked before any device work (the device copies: k_grid_check)
+static int grid_increasing(int n_psi, const double *grid) {
+    for (int k = 1; k < n_psi; k++)
+        if (!(grid[k] > grid[k - 1])) return fail("psi_dP_dV must be strictly increasing");
+    return 0;
+}
+
+// A trace of n > 0 rays with n_dP rows of dP_shell: uploads, allocations, the zeroed dP,
+// `call(d, n_psi, s)` -- the device-pointer trace, its arrays in d as torj_trace_device_ex
+// takes them, n_psi 0 without deposition -- then the downloads (zeros where there was no
+// deposition) and torj_trace_check.  Synchronous.
+template <class F>
+static int trace_staged(torj_plasma_t p, const torj_trace_cfg *cfg, int n, int n_dP, const double *x0,
+                        const double *N0, const double *weights, int n_psi, const double *grid, const double *x_launch,
+                        const double *s0, double *state, int *status, int *steps, double *dP, double *Pdep,
+                        double *traj, F call) {
+    const bool depo = n_psi >= 2 && grid;
+    const size_t rows = (size_t)n_dP * (size_t)(n_psi > 0 ? n_psi + 1 : 1);
+    if (ensure_device(p)) return -1;
+    hipStream_t s = p->stream;
+    const int n_save = cfg->traj_stride > 0 ? cfg->n_steps / cfg->traj_stride : 0;
+    DevBufs B;
+    double *dx0, *dN0, *dw, *dxl, *ds0, *dgrid = nullptr, *ddP = nullptr, *dPdep = nullptr, *dstate, *dtraj;
+    int *dstatus, *dsteps;
+    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s) || B.up(&dw, weights, n, s) ||
+        B.up(&dxl, x_launch, 3 * (size_t)n, s) || B.up(&ds0, s0, n, s))
+        return -1;
+    if (depo) {
+        if (B.up(&dgrid, grid, n_psi, s) || B.alloc(&ddP, rows, true) || B.alloc(&dPdep, n, true)) return -1;
+        HIPCK(hipMemsetAsync(ddP, 0, rows * sizeof(double), s));
+    }
+    if (B.alloc(&dstate, 7 * (size_t)n, true) || B.alloc(&dstatus, n, true) || B.alloc(&dsteps, n, true) ||
+        B.alloc(&dtraj, (size_t)n_save * 5 * n, traj && n_save > 0))
+        return -1;
+    const torj_beam_shard d = {n, dx0, dN0, dw, dgrid, dxl, ds0, dstate, dstatus, dsteps, ddP, dPdep, dtraj, nullptr};
+    if (call(d, depo ? n_psi : 0, s)) return -1;
+    if (ddownload(state, dstate, 7 * (size_t)n, s) || ddownload(status, dstatus, n, s) ||
+        ddownload(steps, dsteps, n, s))
+        return -1;
+    if (depo) {
+        if (ddownload(dP, ddP, rows, s) || ddownload(Pdep, dPdep, n, s)) return -1;
+    } else {
+        if (dP) std::fill(dP, dP + rows, 0.0);
+        if (Pdep) std::fill(Pdep, Pdep + n, 0.0);
+    }
+    if (traj && n_save > 0 && ddownload(traj, dtraj, (size_t)n_save * 5 * n, s)) return -1;
+    return torj_trace_check(p, s);
+}
+
+// The ray entry of n > 0 rays: `call(dx0, dN0, dxp, dNp, ds0, dstatus, s)` is the
+// device-pointer entry.  Synchronous.
+template <class F>
+static int entry_staged(torj_plasma_t p, int n, const double *x0, const double *N0, double *xp, double *Np,
+                        double *s0, int *status, F call) {
+    if (ensure_device(p)) return -1;
+    hipStream_t s = p->stream;
+    DevBufs B;
+    double *dx0, *dN0, *dxp, *dNp, *ds0;
+    int *dst;
+    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s)) return -1;
+    if (B.alloc(&dxp, 3 * (size_t)n, true) || B.alloc(&dNp, 3 * (size_t)n, true) || B.alloc(&ds0, n, true) ||
+        B.alloc(&dst, n, true))
+        return -1;
+    if (call(dx0, dN0, dxp, dNp, ds0, dst, s)) return -1;
+    if (ddownload(xp, dxp, 3 * (size_t)n, s) || ddownload(Np, dNp, 3 * (size_t)n, s) || ddownload(s0, ds0, n, s) ||
+        ddownload(status, dst, n, s))
+        return -1;
+    HIPCK(hipStreamSynchronize(s));
+    return 0;
+}
 
 // ===========================================================================
 // C ABI
@@ -505,21 +578,11 @@ int torj_ray_entry_gpu(torj_plasma_t p, int n, const double *x0, const double *N
                        int mode, double *xp, double *Np, double *s0, int *status) {
     if (!p) return fail("bad plasma handle");
     if (n <= 0) return 0;
-    if (ensure_device(p)) return -1;
-    hipStream_t s = p->stream;
-    DevBufs B;
-    double *dx0, *dN0, *dxp, *dNp, *ds0;
-    int *dst;
-    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s)) return -1;
-    if (B.alloc(&dxp, 3 * (size_t)n, true) || B.alloc(&dNp, 3 * (size_t)n, true) ||
-        B.alloc(&ds0, n, true) || B.alloc(&dst, n, true))
-        return -1;
-    if (torj_ray_entry_device(p, n, dx0, dN0, omega, mode, dxp, dNp, ds0, dst, s)) return -1;
-    if (ddownload(xp, dxp, 3 * (size_t)n, s) || ddownload(Np, dNp, 3 * (size_t)n, s) ||
-        ddownload(s0, ds0, n, s) || ddownload(status, dst, n, s))
-        return -1;
-    HIPCK(hipStreamSynchronize(s));
-    return 0;
+    return entry_staged(p, n, x0, N0, xp, Np, s0, status,
+                        [&](const double *dx0, const double *dN0, double *dxp, double *dNp, double *ds0, int *dst,
+                            hipStream_t s) {
+                            return torj_ray_entry_device(p, n, dx0, dN0, omega, mode, dxp, dNp, ds0, dst, s);
+                        });
 }
 
 int torj_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
@@ -537,44 +600,29 @@ int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, cons
                          void *stream) {
     if (!p || !cfg) return fail("bad plasma handle or cfg");
     if (n <= 0) return 0;
-    if (!stream) {
-        // the NULL (legacy default) stream as the caller's: the trace runs on the
-        // handle's own non-blocking stream, after the NULL stream's earlier work
-        // and before its later work (the same ordering); enqueued on the NULL
-        // stream itself the trace phase ran ~0.4 ms slower per headline launch
-        // (implicit synchronisation with the blocking streams)
-        if (ensure_device(p)) return -1;
-        if (!p->ev_Nin) {
-            HIPCK(hipEventCreateWithFlags(&p->ev_Nin, hipEventDisableTiming));
-            HIPCK(hipEventCreateWithFlags(&p->ev_Nout, hipEventDisableTiming));
+    return on_caller_stream(p, stream, [&](hipStream_t s) {
+        if (p->timing) p->timing_calls++;
+        const bool fit = n_psi >= 2 && grid && dP && cfg->deposition == 1;
+        // TORJ_SPLIT_BATCH=R (read per call; fixed-step absorbing beams): trace in
+        // contiguous batches of R rays (a multiple of 64), each its own pipeline
+        const long sb_rays =
+            (cfg->integrator == 0 && cfg->absorption >= 1) ? env_long("TORJ_SPLIT_BATCH", 0) / 64 * 64 : 0;
+        if ((fit || sb_rays > 0) && cfg->n_steps > 0 && x0 && N0 && state && status && steps) {
+            const size_t per_ray =
+                fit ? fit_bytes_per_ray((size_t)cfg->n_steps + 2, (size_t)n_psi, cfg->integrator == 1) : 0;
+            if (ensure_device(p)) return -1;
+            const size_t nb = batch_rays((size_t)n, per_ray, ws_budget(p), sb_rays);
+            if (nb < (size_t)n)
+                return trace_batched(p, cfg, n, (int)nb, x0, N0, weights, n_psi, grid, x_launch, s0, state, status,
+                                     steps, dP, Pdep, traj, counters, s);
         }
-        HIPCK(hipEventRecord(p->ev_Nin, nullptr));
-        HIPCK(hipStreamWaitEvent(p->stream, p->ev_Nin, 0));
-        const int rc = torj_trace_device_ex(p, cfg, n, x0, N0, weights, n_psi, grid, x_launch, s0, state,
-                                            status, steps, dP, Pdep, traj, counters, p->stream);
-        HIPCK(hipEventRecord(p->ev_Nout, p->stream));
-        HIPCK(hipStreamWaitEvent(nullptr, p->ev_Nout, 0));
-        return rc;
-    }
-    if (p->timing) p->timing_calls++;
-    const bool fit = n_psi >= 2 && grid && dP && cfg->deposition == 1;
-    // TORJ_SPLIT_BATCH=R (read per call; fixed-step absorbing beams): trace in
-    // contiguous batches of R rays (a multiple of 64), each its own pipeline
-    const long sb_rays = (cfg->integrator == 0 && cfg->absorption >= 1) ? env_long("TORJ_SPLIT_BATCH", 0) / 64 * 64 : 0;
-    if ((fit || sb_rays > 0) && cfg->n_steps > 0 && x0 && N0 && state && status && steps) {
-        const size_t per_ray = fit ? fit_bytes_per_ray((size_t)cfg->n_steps + 2, (size_t)n_psi, cfg->integrator == 1) : 0;
-        if (ensure_device(p)) return -1;
-        const size_t nb = batch_rays((size_t)n, per_ray, ws_budget(p), sb_rays);
-        if (nb < (size_t)n)
-            return trace_batched(p, cfg, n, (int)nb, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps,
-                                 dP, Pdep, traj, counters, (hipStream_t)stream);
-    }
-    return trace_device_one(p, cfg, n, x0, N0, weights, n_psi, grid, x_launch, s0, state, status,
-                            steps, dP, Pdep, traj, counters, stream);
+        return trace_device_one(p, cfg, n, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps, dP, Pdep,
+                                traj, counters, s);
+    });
 }
 
 // ---- many beams of differing frequency and mode in one launch (beams_plan, torj_k_beams.hpp),
-// and through differing plasmas (`ps`: beams_plasmas_plan, torj_k_beams_pl.hpp) ----
+// and through differing plasmas (`ps`: beams_plasmas_plan) ----
 }  // extern "C"
 
 static int beams_device_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
@@ -583,28 +631,17 @@ static int beams_device_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_t
                               const double *x_launch, const double *s0, double *state, int *status, int *steps,
                               double *dP, double *Pdep, double *traj, uint64_t *counters, void *stream) {
     if (!p || !cfg) return fail("bad plasma handle or cfg");
-    if (!stream) {  // the NULL stream as the caller's: torj_trace_device_ex's fork and join
-        // (argument errors first, without a device)
+    if (!stream) {  // on_caller_stream's fork needs the device: argument errors first, without one
         BeamsPlasmasPlan pp;
         const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
                                 x_launch != nullptr, s0 != nullptr, traj != nullptr};
         if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
-        if (ensure_device(p)) return -1;
-        if (!p->ev_Nin) {
-            HIPCK(hipEventCreateWithFlags(&p->ev_Nin, hipEventDisableTiming));
-            HIPCK(hipEventCreateWithFlags(&p->ev_Nout, hipEventDisableTiming));
-        }
-        HIPCK(hipEventRecord(p->ev_Nin, nullptr));
-        HIPCK(hipStreamWaitEvent(p->stream, p->ev_Nin, 0));
-        const int rc = beams_device_entry(p, ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid,
-                                          x_launch, s0, state, status, steps, dP, Pdep, traj, counters, p->stream);
-        HIPCK(hipEventRecord(p->ev_Nout, p->stream));
-        HIPCK(hipStreamWaitEvent(nullptr, p->ev_Nout, 0));
-        return rc;
     }
-    if (p->timing) p->timing_calls++;
-    return beams_trace_device(p, ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
-                              state, status, steps, dP, Pdep, traj, counters, (hipStream_t)stream);
+    return on_caller_stream(p, stream, [&](hipStream_t s) {
+        if (p->timing) p->timing_calls++;
+        return beams_trace_device(p, ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch,
+                                  s0, state, status, steps, dP, Pdep, traj, counters, s);
+    });
 }
 
 // host pointers, synchronous, checked
@@ -621,46 +658,18 @@ static int beams_host_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_tra
                                 s0 != nullptr, traj != nullptr};
         if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
     }
-    if (depo)
-        for (int k = 1; k < n_psi; k++)
-            if (!(grid[k] > grid[k - 1])) return fail("psi_dP_dV must be strictly increasing");
+    if (depo && grid_increasing(n_psi, grid)) return -1;
     const int n = beam_off[n_beams];
-    const size_t rows = (size_t)n_beams * (size_t)(n_psi > 0 ? n_psi + 1 : 1);
     if (n == 0) {
-        if (dP) std::fill(dP, dP + rows, 0.0);
+        if (dP) std::fill(dP, dP + (size_t)n_beams * (size_t)(n_psi > 0 ? n_psi + 1 : 1), 0.0);
         return 0;
     }
-    if (ensure_device(p)) return -1;
-    hipStream_t s = p->stream;
-    const int n_save = cfg->traj_stride > 0 ? cfg->n_steps / cfg->traj_stride : 0;
-    DevBufs B;
-    double *dx0, *dN0, *dw = nullptr, *dgrid = nullptr, *dstate, *ddP = nullptr, *dPdep = nullptr, *dtraj = nullptr,
-                       *dxl = nullptr, *ds0 = nullptr;
-    int *dstatus, *dsteps;
-    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s) || B.up(&dw, weights, n, s) ||
-        B.up(&dxl, x_launch, 3 * (size_t)n, s) || B.up(&ds0, s0, n, s))
-        return -1;
-    if (depo) {
-        if (B.up(&dgrid, grid, n_psi, s) || B.alloc(&ddP, rows, true) || B.alloc(&dPdep, n, true)) return -1;
-        HIPCK(hipMemsetAsync(ddP, 0, rows * sizeof(double), s));
-    }
-    if (B.alloc(&dstate, 7 * (size_t)n, true) || B.alloc(&dstatus, n, true) || B.alloc(&dsteps, n, true) ||
-        B.alloc(&dtraj, (size_t)n_save * 5 * n, traj && n_save > 0))
-        return -1;
-    if (beams_device_entry(p, ps, cfg, n_beams, beam_off, omega, mode, dx0, dN0, dw, depo ? n_psi : 0, dgrid, dxl,
-                           ds0, dstate, dstatus, dsteps, ddP, dPdep, dtraj, nullptr, s))
-        return -1;
-    if (ddownload(state, dstate, 7 * (size_t)n, s) || ddownload(status, dstatus, n, s) ||
-        ddownload(steps, dsteps, n, s))
-        return -1;
-    if (depo) {
-        if (ddownload(dP, ddP, rows, s) || ddownload(Pdep, dPdep, n, s)) return -1;
-    } else {
-        if (dP) std::fill(dP, dP + rows, 0.0);
-        if (Pdep) std::fill(Pdep, Pdep + n, 0.0);
-    }
-    if (traj && n_save > 0 && ddownload(traj, dtraj, (size_t)n_save * 5 * n, s)) return -1;
-    return torj_trace_check(p, s);
+    return trace_staged(p, cfg, n, n_beams, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps, dP, Pdep,
+                        traj, [&](const torj_beam_shard &d, int n_psi_d, hipStream_t s) {
+                            return beams_device_entry(p, ps, cfg, n_beams, beam_off, omega, mode, d.x0, d.N0,
+                                                      d.weights, n_psi_d, d.psi_grid, d.x_launch, d.s0, d.state,
+                                                      d.status, d.steps, d.dP_shell, d.P_dep, d.traj, nullptr, s);
+                        });
 }
 
 // the ray entry's argument errors: the tables', then the arrays'; no HIP call
@@ -684,24 +693,24 @@ static int entry_beams_device(torj_plasma_t p, const PlasmaSel *ps, int n_beams,
     if (n == 0) return 0;
     if (ensure_devices(p, ps)) return -1;
     const dim3 grd(nblocks(n, 64)), blk(64);
-    const BeamRec *d_beams;
     EntryArgs a{p->d_coef, p->g, p->psi_prof_max, 0.0, 0, n, x0, N0, xp, Np, s0, status};
+    std::vector<PlasmaRec> plasmas;
+    std::vector<int> beam_pl;
     if (ps) {
-        BeamsPlasmasPlan pp;  // (the two tables the upload takes from it)
-        pp.beam_pl.assign(ps->beam_plasma, ps->beam_plasma + n_beams);
-        for (int j = 0; j < ps->n; j++) pp.plasmas.push_back(kHandleView.rec(ps->list[j]));
-        const PlasmaRec *d_plasmas;
-        const int *d_beam_pl;
-        if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, (hipStream_t)stream, &d_beams, nullptr,
-                         &pp, &d_plasmas, &d_beam_pl))
-            return -1;
-        hipLaunchKernelGGL(k_ray_entry_beams_pl, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams, d_plasmas,
-                           d_beam_pl);
-    } else {
-        if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, (hipStream_t)stream, &d_beams, nullptr))
-            return -1;
-        hipLaunchKernelGGL(k_ray_entry_beams, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams);
+        beam_pl.assign(ps->beam_plasma, ps->beam_plasma + n_beams);
+        for (int j = 0; j < ps->n; j++) plasmas.push_back(kHandleView.rec(ps->list[j]));
     }
+    const BeamRec *d_beams;
+    const PlasmaRec *d_plasmas;
+    const int *d_beam_pl;
+    if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, plasmas, beam_pl, (hipStream_t)stream,
+                     &d_beams, nullptr, &d_plasmas, &d_beam_pl))
+        return -1;
+    if (ps)
+        hipLaunchKernelGGL(k_ray_entry_beams, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams, d_plasmas,
+                           d_beam_pl);
+    else
+        hipLaunchKernelGGL(k_ray_entry_beams, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -712,21 +721,12 @@ static int entry_beams_host(torj_plasma_t p, const PlasmaSel *ps, int n_beams, c
     if (entry_beams_check(p, ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status)) return -1;
     const int n = beam_off[n_beams];
     if (n == 0) return 0;
-    if (ensure_device(p)) return -1;
-    hipStream_t s = p->stream;
-    DevBufs B;
-    double *dx0, *dN0, *dxp, *dNp, *ds0;
-    int *dst;
-    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s)) return -1;
-    if (B.alloc(&dxp, 3 * (size_t)n, true) || B.alloc(&dNp, 3 * (size_t)n, true) || B.alloc(&ds0, n, true) ||
-        B.alloc(&dst, n, true))
-        return -1;
-    if (entry_beams_device(p, ps, n_beams, beam_off, omega, mode, dx0, dN0, dxp, dNp, ds0, dst, s)) return -1;
-    if (ddownload(xp, dxp, 3 * (size_t)n, s) || ddownload(Np, dNp, 3 * (size_t)n, s) || ddownload(s0, ds0, n, s) ||
-        ddownload(status, dst, n, s))
-        return -1;
-    HIPCK(hipStreamSynchronize(s));
-    return 0;
+    return entry_staged(p, n, x0, N0, xp, Np, s0, status,
+                        [&](const double *dx0, const double *dN0, double *dxp, double *dNp, double *ds0, int *dst,
+                            hipStream_t s) {
+                            return entry_beams_device(p, ps, n_beams, beam_off, omega, mode, dx0, dN0, dxp, dNp, ds0,
+                                                      dst, s);
+                        });
 }
 
 extern "C" {
@@ -807,8 +807,7 @@ int torj_power_deposition_profile(torj_plasma_t p, int n_rays, const int *n_poin
     if (n_rays < 0 || n_psi < 2 || !grid) return fail("power_deposition_profile: n_rays >= 0, n_psi >= 2 needed");
     if (n_rays == 0) return 0;
     if (!n_points || !s || !x || !dP_ds || !dP_dV || !P) return fail("power_deposition_profile: null argument");
-    for (int k = 1; k < n_psi; k++)
-        if (!(grid[k] > grid[k - 1])) return fail("psi_dP_dV must be strictly increasing");
+    if (grid_increasing(n_psi, grid)) return -1;
     std::vector<long> off(n_rays);
     long tot = 0;
     int rows = 0;
@@ -978,54 +977,14 @@ int torj_trace_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const doubl
                   int *steps, double *dP, double *Pdep, double *traj) {
     if (!p || !cfg) return fail("bad plasma handle or cfg");
     if (n <= 0) return 0;
-    const bool depo = n_psi >= 2 && grid;
-    if (depo)  // host copy at hand: checked before any device work
-        for (int k = 1; k < n_psi; k++)
-            if (!(grid[k] > grid[k - 1])) return fail("psi_dP_dV must be strictly increasing");
-    if (ensure_device(p)) return -1;
-    hipStream_t s = p->stream;
-    const int n_save = cfg->traj_stride > 0 ? cfg->n_steps / cfg->traj_stride : 0;
-    DevBufs B;
-    double *dx0, *dN0, *dw = nullptr, *dgrid = nullptr, *dstate, *ddP = nullptr, *dPdep = nullptr,
-                                *dtraj = nullptr;
-    int *dstatus, *dsteps;
-    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s)) return -1;
-    if (weights) {
-        if (B.up(&dw, weights, n, s)) return -1;
-    }
-    if (depo) {
-        if (B.up(&dgrid, grid, n_psi, s) || B.alloc(&ddP, n_psi + 1, true) ||
-            B.alloc(&dPdep, n, true))
-            return -1;
-        HIPCK(hipMemsetAsync(ddP, 0, (n_psi + 1) * sizeof(double), s));
-    }
-    if (B.alloc(&dstate, 7 * (size_t)n, true) || B.alloc(&dstatus, n, true) ||
-        B.alloc(&dsteps, n, true))
-        return -1;
-    if (traj && n_save > 0) {
-        if (B.alloc(&dtraj, (size_t)n_save * 5 * n, true)) return -1;
-    }
-    double *dxl = nullptr, *ds0 = nullptr;
-    if (x_launch) {
-        if (B.up(&dxl, x_launch, 3 * (size_t)n, s)) return -1;
-    }
-    if (s0) {
-        if (B.up(&ds0, s0, n, s)) return -1;
-    }
-    if (torj_trace_device_ex(p, cfg, n, dx0, dN0, dw, depo ? n_psi : 0, dgrid, dxl, ds0, dstate,
-                             dstatus, dsteps, ddP, dPdep, dtraj, nullptr, s))
-        return -1;
-    if (ddownload(state, dstate, 7 * (size_t)n, s) || ddownload(status, dstatus, n, s) ||
-        ddownload(steps, dsteps, n, s))
-        return -1;
-    if (depo) {
-        if (ddownload(dP, ddP, n_psi + 1, s) || ddownload(Pdep, dPdep, n, s)) return -1;
-    } else {
-        if (dP) std::fill(dP, dP + (n_psi > 0 ? n_psi + 1 : 1), 0.0);
-        if (Pdep) std::fill(Pdep, Pdep + n, 0.0);
-    }
-    if (traj && n_save > 0 && ddownload(traj, dtraj, (size_t)n_save * 5 * n, s)) return -1;
-    return torj_trace_check(p, s);
+    // (the grid's host copy is at hand: checked before any device work)
+    if (n_psi >= 2 && grid && grid_increasing(n_psi, grid)) return -1;
+    return trace_staged(p, cfg, n, 1, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps, dP, Pdep, traj,
+                        [&](const torj_beam_shard &d, int n_psi_d, hipStream_t s) {
+                            return torj_trace_device_ex(p, cfg, n, d.x0, d.N0, d.weights, n_psi_d, d.psi_grid,
+                                                        d.x_launch, d.s0, d.state, d.status, d.steps, d.dP_shell,
+                                                        d.P_dep, d.traj, nullptr, s);
+                        });
 }
 
 int torj_trace_beam(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
@@ -1041,8 +1000,7 @@ int torj_trace_beam(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const dou
     if (!x0 || !N0 || !state || !status || !steps) return fail("x0, N0, state, status, steps required");
     const bool depo = n_psi >= 2 && grid;
     if (depo) {
-        for (int k = 1; k < n_psi; k++)
-            if (!(grid[k] > grid[k - 1])) return fail("psi_dP_dV must be strictly increasing");
+        if (grid_increasing(n_psi, grid)) return -1;
         if (!dP || !Pdep) return fail("deposition needs dP_shell and P_dep");
     }
     const bool same = beam_same_device();

@@ -6,6 +6,20 @@
 // k_trace's on that beam alone, and the beam's omega, Consts and mode are
 // uniform over the wave (scalar loads by blockIdx, SGPRs as k_trace's kernel
 // arguments are).  The device functions are k_trace's, unchanged.
+// Beams that go through differing plasmas (BeamsPlArgs; torj_launch.hpp
+// beams_plasmas_plan): beam b is traced through the listed plasma beam_pl[b], whose
+// coefficients, cell table and grid replace the handle's in the trace's arguments.  A
+// wave never mixes beams, so its plasma is wave-uniform like its omega: k_trace_beams
+// loads the record by blockIdx (scalar loads, SGPRs).  The kernels after the trace run
+// one lane per ray and look the ray's beam up, then that beam's plasma.
+// Each kernel is written once for both: a template on the argument struct, BeamsArgs
+// or BeamsPlArgs (beam_args is overloaded on the two), or, where the arguments are
+// loose, on a trailing pack that is empty or the two plasma tables (beam_plasma
+// likewise); k_fit_depo_pl is the plasma form of k_fit_depo itself.  The bodies repeat
+// their single-beam kernels' (k_trace, k_final_alpha, k_ray_entry, k_fit_depo) and are
+// not one function with them: a shared __forceinline__ body is optimised on its own
+// before it is inlined and gave those kernels other registers and schedules
+// (profiles/r14/kernels_asm.txt).  A fix to one of the four is made there and here.
 // (a slice of torj_hip.hip: included after `using namespace torj`)
 #pragma once
 #include "torj_args.hpp"
@@ -36,9 +50,39 @@ __device__ __forceinline__ TraceArgs beam_args(const BeamsArgs &ba, int b, const
     return a;
 }
 
-// grid: the wave table's entries; 64 lanes
-template <int ABS, int DEPO, bool TRAJ, int LPR = 1>
-__global__ void __launch_bounds__(64, TORJ_MIN_WAVES) k_trace_beams(BeamsArgs ba) {
+// plasma j's record.  A pointer read from a table in memory is a flat one to the
+// compiler (a kernel's own pointer arguments it knows to be global), and the loads
+// through it would be flat_load where the single-plasma kernels have global_load.  So
+// the record's two pointers are read as what they are, global pointers, and only then
+// handed on as plain ones: the address space then follows them into the device functions.
+__device__ __forceinline__ PlasmaRec plasma_rec(const PlasmaRec *plasmas, int j) {
+    typedef const __attribute__((address_space(1))) double *gptr;
+    const PlasmaRec *q = plasmas + j;
+    gptr coef, cellp;
+    __builtin_memcpy(&coef, &q->coef, sizeof(coef));
+    __builtin_memcpy(&cellp, &q->cellp, sizeof(cellp));
+    return PlasmaRec{(const double *)coef, (const double *)cellp, q->g, q->psi_max};
+}
+
+// beam_args with the beam's plasma in place of the handle's
+__device__ __forceinline__ TraceArgs beam_args(const BeamsPlArgs &pa, int b, const BeamRec &br) {
+    TraceArgs a = beam_args((const BeamsArgs &)pa, b, br);
+    const PlasmaRec pr = plasma_rec(pa.plasmas, pa.beam_pl[b]);
+    a.coef = pr.coef, a.cellp = pr.cellp, a.g = pr.g;
+    return a;
+}
+
+// the plasma beam b goes through: the one in the kernel's own arguments, or the
+// listed one the tables name
+__device__ __forceinline__ PlasmaRec beam_plasma(const PlasmaRec &own, int) { return own; }
+__device__ __forceinline__ PlasmaRec beam_plasma(const PlasmaRec &, int b, const PlasmaRec *plasmas,
+                                                 const int *beam_pl) {
+    return plasma_rec(plasmas, beam_pl[b]);
+}
+
+// grid: the wave table's entries; 64 lanes.  BA: BeamsArgs or BeamsPlArgs
+template <int ABS, int DEPO, bool TRAJ, int LPR, class BA>
+__global__ void __launch_bounds__(64, TORJ_MIN_WAVES) k_trace_beams(BA ba) {
     const BeamWave wv = ba.waves[blockIdx.x];
     const BeamRec br = ba.beams[wv.beam];
     const TraceArgs a = beam_args(ba, wv.beam, br);
@@ -59,22 +103,23 @@ __global__ void __launch_bounds__(64, TORJ_MIN_WAVES) k_trace_beams(BeamsArgs ba
     flush_counters(a, steps, 4ull * steps, work);
 }
 
-// k_final_alpha with the ray's beam's constants
-template <int ABS>
-__global__ void __launch_bounds__(64) k_final_alpha_beams(BeamsArgs ba) {
+// k_final_alpha with the ray's beam's constants and plasma
+template <int ABS, class BA>
+__global__ void __launch_bounds__(64) k_final_alpha_beams(BA ba) {
     const TraceArgs &a = ba.a;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= a.n) return;
     const int k = a.steps[i];
     if (k <= 0) return;
-    const BeamRec br = ba.beams[beam_of(ba.beams, ba.n_beams, i)];
+    const int b = beam_of(ba.beams, ba.n_beams, i);
+    const TraceArgs ab = beam_args(ba, b, ba.beams[b]);
     double x[3], N[3], du[6], al = 0.0;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         x[c] = a.state[c * a.n + i];
         N[c] = a.state[(3 + c) * a.n + i];
     }
-    if constexpr (ABS != 0) ray_rhs_m<ABS>(a.coef, a.g, br.k, c_gl, br.omega, br.mode, a.abs_model, x, N, du, al, nullptr);
+    if constexpr (ABS != 0) ray_rhs_m<ABS>(ab.coef, ab.g, ab.k, c_gl, ab.omega, ab.mode, a.abs_model, x, N, du, al, nullptr);
     a.smp_dpds[smp_at(k, i, a.smp_rows)] = exp(-a.state[6 * a.n + i]) * al;
 }
 
@@ -116,17 +161,21 @@ __global__ void __launch_bounds__(256) k_shell_sum_beams(FitArgs a, const BeamRe
     }
 }
 
-// k_ray_entry with the ray's beam's frequency and mode (a.omega, a.mode unused)
-__global__ void __launch_bounds__(64) k_ray_entry_beams(EntryArgs a, const BeamRec *beams, int n_beams) {
+// k_ray_entry with the ray's beam's frequency and mode (a.omega, a.mode unused) and,
+// with the tables (PT: none, or plasmas and beam_pl), its plasma and that plasma's psi_prof_max
+// (a.coef, a.g, a.psi_max then unused too)
+template <class... PT>
+__global__ void __launch_bounds__(64) k_ray_entry_beams(EntryArgs a, const BeamRec *beams, int n_beams, PT... pt) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= a.n) return;
     const int b = beam_of(beams, n_beams, i);
     const double omega = beams[b].omega;
     const int mode = beams[b].mode;
+    const PlasmaRec pr = beam_plasma(PlasmaRec{a.coef, nullptr, a.g, a.psi_max}, b, pt...);
     const double x0[3] = {a.x0[i], a.x0[a.n + i], a.x0[2 * a.n + i]};
     const double N0[3] = {a.N0[i], a.N0[a.n + i], a.N0[2 * a.n + i]};
     double xo[3], No[3], s0;
-    const int st = ray_entry_one(a.coef, a.g, a.psi_max, x0, N0, omega, mode, xo, No, s0);
+    const int st = ray_entry_one(pr.coef, pr.g, pr.psi_max, x0, N0, omega, mode, xo, No, s0);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         a.xp[k * a.n + i] = xo[k];
@@ -134,4 +183,21 @@ __global__ void __launch_bounds__(64) k_ray_entry_beams(EntryArgs a, const BeamR
     }
     a.s0[i] = s0;
     a.status[i] = st;
+}
+
+// k_fit_depo with psi at the launch point from the ray's beam's plasma (a.coef, a.g
+// unused); the walk itself runs on the ray's samples
+__global__ void __launch_bounds__(64, 2) k_fit_depo_pl(FitArgs a, const BeamRec *beams, int n_beams,
+                                                       const PlasmaRec *plasmas, const int *beam_pl) {
+    extern __shared__ double s_grid[];
+    if (a.n_psi <= kFitGridLds) {
+        for (int k = threadIdx.x; k < a.n_psi; k += 64) s_grid[k] = a.grid[k];
+        __syncthreads();
+        a.grid = s_grid;
+    }
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.n) return;
+    const PlasmaRec pr = plasma_rec(plasmas, beam_pl[beam_of(beams, n_beams, i)]);
+    const double xl[3] = {a.x_launch[i], a.x_launch[a.n + i], a.x_launch[2 * a.n + i]};
+    fit_depo_ray<kOpenCache>(a, i, psi_at(pr.coef, pr.g, xl));
 }

@@ -7,8 +7,10 @@
 // trace_device_one enqueues what the plan says, one short launcher per path;
 // trace_batched is torj_trace_device_ex's loop over ray batches; beams_plan and
 // beams_trace_device are the same two steps for a multi-beam launch, and
-// beams_plasmas_plan adds a plasma per beam to that plan.  Also here,
-// ahead of its first user: the Gauss-Legendre table's upload.
+// beams_plasmas_plan adds a plasma per beam to that plan.  trace_prologue is what
+// both enqueue ahead of their trace kernels, on_caller_stream the NULL stream's
+// fork and join around either.  Also here, ahead of its first user: the
+// Gauss-Legendre table's upload.
 // The planning comes first and needs no kernel header: TORJ_LAUNCH_PLAN_ONLY
 // stops there (the CPU test's harness).
 // (a slice of torj_hip.hip: included after `using namespace torj`)
@@ -330,7 +332,6 @@ static int beams_plasmas_plan(BeamsPlasmasPlan &pp, const torj_trace_cfg &cfg, i
 
 #include "torj_dispatch.hpp"
 #include "torj_k_beams.hpp"
-#include "torj_k_beams_pl.hpp"
 #include "torj_k_fused.hpp"
 #include "torj_k_points.hpp"
 #include "torj_split.hpp"
@@ -433,6 +434,27 @@ static int timing_begin(torj_plasma_s *p, hipEvent_t ev[3], hipStream_t s) {
     return 0;
 }
 
+// A device-pointer entry's stream: call(s) with the caller's, or, for the NULL (legacy
+// default) stream, with the handle's own non-blocking stream, after the NULL stream's
+// earlier work and before its later work (the same ordering); enqueued on the NULL
+// stream itself the trace phase ran ~0.4 ms slower per headline launch (implicit
+// synchronisation with the blocking streams)
+template <class F>
+static int on_caller_stream(torj_plasma_s *p, void *stream, F call) {
+    if (stream) return call((hipStream_t)stream);
+    if (ensure_device(p)) return -1;
+    if (!p->ev_Nin) {
+        HIPCK(hipEventCreateWithFlags(&p->ev_Nin, hipEventDisableTiming));
+        HIPCK(hipEventCreateWithFlags(&p->ev_Nout, hipEventDisableTiming));
+    }
+    HIPCK(hipEventRecord(p->ev_Nin, nullptr));
+    HIPCK(hipStreamWaitEvent(p->stream, p->ev_Nin, 0));
+    const int rc = call(p->stream);
+    HIPCK(hipEventRecord(p->ev_Nout, p->stream));
+    HIPCK(hipStreamWaitEvent(nullptr, p->ev_Nout, 0));
+    return rc;
+}
+
 // the kernels' arguments that come from the handle, the cfg and the caller's arrays alone
 static TraceArgs trace_args(const torj_plasma_s *p, const torj_trace_cfg &cfg, int n, const double *x0,
                             const double *N0, const double *weights, const double *s0, double *state,
@@ -461,6 +483,41 @@ static void fit_args(FitArgs &fa, const TraceArgs &a, const double *x_launch, bo
     fa.dP = a.dP, fa.Pray = a.Pdep;
 }
 
+// What a launch sets up and enqueues ahead of its trace kernels, from either plan
+// (LaunchPlan, BeamsPlan: depo, fit, tr, n_save, lay): the deposition's arguments with
+// the P_dep workspace, the walk's workspace and arguments, then in `s`'s order
+// k_grid_check, the NaN fill of traj, fit_zero and the timing's first event.
+// zero = false leaves fit_zero to the caller.
+template <class Plan>
+static int trace_prologue(torj_plasma_s *p, const Plan &pl, const torj_trace_cfg &cfg, int n_psi, const double *grid,
+                          const double *x_launch, double *dP, double *Pdep, double *traj, bool s_uniform, bool zero,
+                          TraceArgs &a, FitArgs &fa, hipEvent_t ev[3], hipStream_t s) {
+    if (pl.depo) {
+        a.n_psi = n_psi;
+        a.grid = grid;  // uniform-grid fast path is set up in-kernel from grid[0], grid[n-1]
+        a.dP = dP;
+        if (!Pdep) {  // the work-queue kernel carries P_dep across chunks: workspace
+            if (ensure_buf(p, p->ws, (size_t)a.n * sizeof(double))) return -1;
+            Pdep = (double *)p->ws.d;
+        }
+        a.Pdep = Pdep;
+    }
+    if (pl.fit) {
+        if (ensure_buf(p, p->fit, pl.lay.bytes())) return -1;
+        fit_point(pl.lay, (char *)p->fit.d, fa, &a);
+        fit_args(fa, a, x_launch, s_uniform);
+    }
+    if (pl.depo)  // psi_dP_dV strictly increasing: checked on the device, reported by torj_trace_check
+        hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
+    if (pl.tr) {
+        a.traj_stride = cfg.traj_stride, a.n_save = pl.n_save, a.traj = traj;
+        if (a.n_save > 0)
+            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * a.n * sizeof(double), s));  // NaN
+    }
+    if (pl.fit && zero && fit_zero(fa, s)) return -1;
+    return timing_begin(p, ev, s);
+}
+
 // one launch of the hot path over n rays (the body of torj_trace_device_ex)
 static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
                             const double *N0, const double *weights, int n_psi, const double *grid,
@@ -482,35 +539,14 @@ static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, c
         if (ensure_buf(p, p->chunk, (size_t)n * sizeof(int))) return -1;
         a.chunk = (int *)p->chunk.d;
     }
-    if (pl.depo) {
-        a.n_psi = n_psi;
-        a.grid = grid;  // uniform-grid fast path is set up in-kernel from grid[0], grid[n-1]
-        a.dP = dP;
-        if (!Pdep) {  // the work-queue kernel carries P_dep across chunks: workspace
-            if (ensure_buf(p, p->ws, (size_t)n * sizeof(double))) return -1;
-            Pdep = (double *)p->ws.d;
-        }
-        a.Pdep = Pdep;
-    }
-    FitArgs fa{};
-    if (pl.fit) {
-        if (ensure_buf(p, p->fit, pl.lay.bytes())) return -1;
-        fit_point(pl.lay, (char *)p->fit.d, fa, &a);
-        fit_args(fa, a, x_launch, !pl.adaptive);
-    }
-    if (pl.depo)  // psi_dP_dV strictly increasing: checked on the device, reported by torj_trace_check
-        hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
-    if (pl.tr) {
-        a.traj_stride = cfg->traj_stride, a.n_save = pl.n_save, a.traj = traj;
-        if (a.n_save > 0)
-            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * n * sizeof(double), s));  // NaN
-    }
     // the fused / queue paths clear the deposition workspace before the trace
     // phase's first event (outside trace_ms, as before round 5); the split path
     // clears it on its scan stream, overlapped with the first trajectory block
-    if (pl.fit && pl.path != kPathSplit && fit_zero(fa, s)) return -1;
+    FitArgs fa{};
     hipEvent_t ev[3];
-    if (timing_begin(p, ev, s)) return -1;
+    if (trace_prologue(p, pl, *cfg, n_psi, grid, x_launch, dP, Pdep, traj, !pl.adaptive, pl.path != kPathSplit, a, fa,
+                       ev, s))
+        return -1;
     DepoStream dstr{};  // the split pipeline's streamed deposition (split_trace)
     switch (pl.path) {
     case kPathSplit:
@@ -533,25 +569,26 @@ static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, c
 // the plan's tables into the handle's buffer, in `s`'s order: the beams' records, then
 // the waves'.  The copy is from pageable memory, which HIP has consumed when the call
 // returns; the buffer is the handle's scratch (one stream per handle), so a launch
-// enqueued earlier on `s` has read its own tables before these arrive.
+// enqueued earlier on `s` has read its own tables before these arrive.  `plasmas` and
+// `beam_pl` are empty unless the launch goes through several plasmas.
 static int beams_upload(torj_plasma_s *p, const std::vector<BeamRec> &beams, const std::vector<BeamWave> &waves,
-                        hipStream_t s, const BeamRec **d_beams, const BeamWave **d_waves,
-                        const BeamsPlasmasPlan *pp = nullptr, const PlasmaRec **d_plasmas = nullptr,
-                        const int **d_beam_pl = nullptr) {
+                        const std::vector<PlasmaRec> &plasmas, const std::vector<int> &beam_pl, hipStream_t s,
+                        const BeamRec **d_beams, const BeamWave **d_waves, const PlasmaRec **d_plasmas,
+                        const int **d_beam_pl) {
     // (every table's size is a multiple of 8 bytes but the last's, so each starts aligned)
     const size_t nb = beams.size() * sizeof(BeamRec), nw = waves.size() * sizeof(BeamWave);
-    const size_t np = pp ? pp->plasmas.size() * sizeof(PlasmaRec) : 0, ni = pp ? pp->beam_pl.size() * sizeof(int) : 0;
+    const size_t np = plasmas.size() * sizeof(PlasmaRec), ni = beam_pl.size() * sizeof(int);
     if (ensure_buf(p, p->beams, nb + nw + np + ni)) return -1;
     char *d = (char *)p->beams.d;
     *d_beams = (const BeamRec *)d;
     if (d_waves) *d_waves = (const BeamWave *)(d + nb);
-    if (pp) {  // a launch through several plasmas: their records and the beams' indices behind the two,
+    if (np) {  // a launch through several plasmas: their records and the beams' indices behind the two,
         // all four tables packed and sent as one copy
         std::vector<char> h(nb + nw + np + ni);
         if (nb) memcpy(h.data(), beams.data(), nb);
         if (nw) memcpy(h.data() + nb, waves.data(), nw);
-        memcpy(h.data() + nb + nw, pp->plasmas.data(), np);
-        if (ni) memcpy(h.data() + nb + nw + np, pp->beam_pl.data(), ni);
+        memcpy(h.data() + nb + nw, plasmas.data(), np);
+        if (ni) memcpy(h.data() + nb + nw + np, beam_pl.data(), ni);
         HIPCK(hipMemcpyAsync(d, h.data(), h.size(), hipMemcpyHostToDevice, s));
         *d_plasmas = (const PlasmaRec *)(d + nb + nw);
         *d_beam_pl = (const int *)(d + nb + nw + np);
@@ -594,30 +631,40 @@ static int ensure_devices(torj_plasma_s *p, const PlasmaSel *ps) {
     return ensure_device(p);
 }
 
-// k_trace_beams' instance: k_trace's set (launch_lanes)
-static void launch_beams(const BeamsArgs &ba, const BeamsPlan &bp, hipStream_t s) {
-    const dim3 grd((unsigned)bp.waves.size()), blk(64);
-    if (bp.lpr == 16)
-        with_depo_traj(bp.DM, bp.tr, [&](auto D, auto T) {
-            if constexpr (D() != kDepoBinned) hipLaunchKernelGGL((k_trace_beams<1, D(), T(), 16>), grd, blk, 0, s, ba);
-        });
-    else
-        with_abs_depo_traj(ba.a.abs_model == 1 ? 1 : 0, bp.DM, bp.tr, [&](auto A, auto D, auto T) {
-            if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace_beams<A(), D(), T()>), grd, blk, 0, s, ba);
-        });
-}
-// k_trace_beams_pl's: the same set
-static void launch_beams_pl(const BeamsPlArgs &pa, const BeamsPlan &bp, hipStream_t s) {
+// k_trace_beams' instance: k_trace's set (launch_lanes).  BA: BeamsArgs, or BeamsPlArgs through several plasmas
+template <class BA>
+static void launch_beams(const BA &ba, const BeamsPlan &bp, hipStream_t s) {
     const dim3 grd((unsigned)bp.waves.size()), blk(64);
     if (bp.lpr == 16)
         with_depo_traj(bp.DM, bp.tr, [&](auto D, auto T) {
             if constexpr (D() != kDepoBinned)
-                hipLaunchKernelGGL((k_trace_beams_pl<1, D(), T(), 16>), grd, blk, 0, s, pa);
+                hipLaunchKernelGGL((k_trace_beams<1, D(), T(), 16, BA>), grd, blk, 0, s, ba);
         });
     else
-        with_abs_depo_traj(pa.b.a.abs_model == 1 ? 1 : 0, bp.DM, bp.tr, [&](auto A, auto D, auto T) {
-            if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace_beams_pl<A(), D(), T()>), grd, blk, 0, s, pa);
+        with_abs_depo_traj(ba.a.abs_model == 1 ? 1 : 0, bp.DM, bp.tr, [&](auto A, auto D, auto T) {
+            if constexpr (A() <= 1) hipLaunchKernelGGL((k_trace_beams<A(), D(), T(), 1, BA>), grd, blk, 0, s, ba);
         });
+}
+
+// launch_post with the beams' kernels; the walk takes psi at the launch point from the
+// handle's plasma (k_fit_depo itself) or from the ray's beam's
+static void launch_fit_depo(const BeamsArgs &, const FitArgs &fa, dim3 grd, hipStream_t s) {
+    hipLaunchKernelGGL(k_fit_depo, grd, dim3(64), fit_grid_lds(fa.n_psi), s, fa);
+}
+static void launch_fit_depo(const BeamsPlArgs &pa, const FitArgs &fa, dim3 grd, hipStream_t s) {
+    hipLaunchKernelGGL(k_fit_depo_pl, grd, dim3(64), fit_grid_lds(fa.n_psi), s, fa, pa.beams, pa.n_beams, pa.plasmas,
+                       pa.beam_pl);
+}
+template <class BA>
+static int launch_post_beams(const BA &ba, const FitArgs &fa, hipStream_t s) {
+    const dim3 grd(nblocks(ba.a.n, 64)), blk(64);
+    with_abs(ba.a.abs_model, [&](auto A) {
+        if constexpr (A() <= 1) hipLaunchKernelGGL((k_final_alpha_beams<A(), BA>), grd, blk, 0, s, ba);
+    });
+    launch_fit_depo(ba, fa, grd, s);
+    hipLaunchKernelGGL(k_shell_sum_beams, dim3(fa.n_psi, ba.n_beams), dim3(256), 0, s, fa, ba.beams);
+    HIPCK(hipGetLastError());
+    return 0;
 }
 
 // one multi-beam launch on stream `s` (the body of torj_trace_beams_device and, with
@@ -648,63 +695,26 @@ static int beams_trace_device(torj_plasma_t p, const PlasmaSel *ps, const torj_t
                         n, bp.lay.bytes(), budget);
     }
     BeamsPlArgs pa{};
-    BeamsArgs &ba = pa.b;
+    BeamsArgs &ba = pa;
     torj_trace_cfg c1 = *cfg;  // (omega and mode are the beams'; any valid pair here)
     c1.omega = omega[0], c1.mode = mode[0];
     // (with plasmas a.coef, a.cellp and a.g are p's and unused: the beam's plasma record gives them)
     TraceArgs &a = ba.a = trace_args(p, c1, n, x0, N0, weights, s0, state, status, steps, counters);
     ba.n_beams = n_beams;
-    if (beams_upload(p, bp.beams, bp.waves, s, &ba.beams, &ba.waves, ps ? &pp : nullptr, &pa.plasmas, &pa.beam_pl))
+    if (beams_upload(p, bp.beams, bp.waves, pp.plasmas, pp.beam_pl, s, &ba.beams, &ba.waves, &pa.plasmas, &pa.beam_pl))
         return -1;
-    if (bp.depo) {
-        a.n_psi = n_psi, a.grid = grid, a.dP = dP;
-        if (!Pdep) {
-            if (ensure_buf(p, p->ws, (size_t)n * sizeof(double))) return -1;
-            Pdep = (double *)p->ws.d;
-        }
-        a.Pdep = Pdep;
-    }
     FitArgs fa{};
-    if (bp.fit) {
-        if (ensure_buf(p, p->fit, bp.lay.bytes())) return -1;
-        fit_point(bp.lay, (char *)p->fit.d, fa, &a);
-        fit_args(fa, a, x_launch, true);
-    }
-    if (bp.depo) hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
-    if (bp.tr) {
-        a.traj_stride = cfg->traj_stride, a.n_save = bp.n_save, a.traj = traj;
-        if (a.n_save > 0)
-            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * n * sizeof(double), s));  // NaN
-    }
-    if (bp.fit && fit_zero(fa, s)) return -1;
     hipEvent_t ev[3];
-    if (timing_begin(p, ev, s)) return -1;
-    if (ps)
-        launch_beams_pl(pa, bp, s);
-    else
-        launch_beams(ba, bp, s);
-    HIPCK(hipGetLastError());
-    if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
-    if (bp.fit) {  // launch_post with the beams' kernels
-        const dim3 grd(nblocks(n, 64)), blk(64);
-        with_abs(a.abs_model, [&](auto A) {
-            if constexpr (A() <= 1) {
-                if (ps)
-                    hipLaunchKernelGGL(k_final_alpha_beams_pl<A()>, grd, blk, 0, s, pa);
-                else
-                    hipLaunchKernelGGL(k_final_alpha_beams<A()>, grd, blk, 0, s, ba);
-            }
-        });
-        if (ps)
-            hipLaunchKernelGGL(k_fit_depo_pl, grd, blk, fit_grid_lds(fa.n_psi), s, fa, ba.beams, n_beams, pa.plasmas,
-                               pa.beam_pl);
-        else
-            hipLaunchKernelGGL(k_fit_depo, grd, blk, fit_grid_lds(fa.n_psi), s, fa);
-        hipLaunchKernelGGL(k_shell_sum_beams, dim3(fa.n_psi, n_beams), dim3(256), 0, s, fa, ba.beams);
+    if (trace_prologue(p, bp, *cfg, n_psi, grid, x_launch, dP, Pdep, traj, true, true, a, fa, ev, s)) return -1;
+    auto run = [&](const auto &args) -> int {  // the trace and the phase after it, on either argument struct
+        launch_beams(args, bp, s);
         HIPCK(hipGetLastError());
-    }
-    if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
-    return 0;
+        if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
+        if (bp.fit && launch_post_beams(args, fa, s)) return -1;
+        if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
+        return 0;
+    };
+    return ps ? run(pa) : run(ba);
 }
 
 // ---- ray batches (torj_trace_device_ex): the beam in contiguous batches of nb
