@@ -1070,11 +1070,21 @@ static int first_point(const or_plasma *p, const double x0[3], const double N0[3
     }
     double t = (fabs(ga) <= fabs(gb)) ? a : b;
 #undef G
+    double ps[3] = {pp[0], pp[1], pp[2]};
     for (int k = 0; k < 3; k++) pp[k] += t * N0[k];
     double psi_ref = or_evaluate(&p->psi, pp);
     if (!(fabs(psi_ref - p->psi_prof_max) < 1e-6)) return OR_ENTRY_FAIL; /* :32 */
-    if (psi_ref > p->psi_prof_max)
+    if (psi_ref > p->psi_prof_max) {
         for (int k = 0; k < 3; k++) pp[k] += 2.0 * (psi_ref - p->psi_prof_max) * N0[k];
+        /* bisected to machine precision (not the reference's xtol = 1e-6),
+         * psi_ref - psi_max can be one rounding error and the step above less
+         * than an ulp of the coordinates; psi then stays above psi_max and :138
+         * would refuse a sound ray, depending on the toroidal angle.  The
+         * bracket's other end, where g < 0, is then the entry point. */
+        double t_in = ga < 0 ? a : b;
+        if ((ga < 0 || gb < 0) && or_evaluate(&p->psi, pp) > p->psi_prof_max)
+            for (int k = 0; k < 3; k++) pp[k] = ps[k] + t_in * N0[k];
+    }
     for (int k = 0; k < 3; k++) out[k] = pp[k];
     return OR_OK;
 }

@@ -48,4 +48,21 @@ int spl_plan(long long n, int n_steps, int chunk_steps, int abs_model, int count
     out[k++] = (unsigned long long)(uintptr_t)end;
     return k;
 }
+
+// the trajectory kernel the plan of an n-ray Albajar call picks on an nR x nZ grid
+// under the environment's TORJ_TRAJ_LDS (kTrajL2 .. kTrajCell), and k_traj_lds'
+// dynamic LDS bytes for that grid
+int spl_traj_mode(long long n, int nR, int nZ, unsigned long long *lds_bytes) {
+    TraceArgs a{};
+    a.n = (int)n;
+    a.n_steps = 6000;
+    a.chunk_steps = 60;
+    a.abs_model = 1;
+    a.g.nR = nR;
+    a.g.nZ = nZ;
+    SplitPlan pl;
+    split_plan_sizes(pl, 3, 60, (size_t)64 << 30, a, kDepoSamples, true, true);
+    *lds_bytes = pl.traj_lds_bytes;
+    return pl.traj_mode;
+}
 }

@@ -29,7 +29,46 @@ def H():
     L = C.CDLL(out)
     L.spl_plan.argtypes = [C.c_longlong] + [C.c_int] * 9 + [C.c_ulonglong, C.c_ulonglong,
                                                            C.POINTER(C.c_ulonglong)]
+    L.spl_traj_mode.argtypes = [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
     return L
+
+
+def traj_mode(H, n, nR, nZ, lds):
+    """(the trajectory kernel the plan picks for n rays on an nR x nZ grid under
+    TORJ_TRAJ_LDS = lds: 0 k_traj, 1 k_traj_lds, 2 k_traj_tile, 3 k_traj_cell; k_traj_lds'
+    dynamic LDS bytes on that grid)"""
+    old = os.environ.get("TORJ_TRAJ_LDS")
+    try:
+        if lds is None:
+            os.environ.pop("TORJ_TRAJ_LDS", None)
+        else:
+            os.environ["TORJ_TRAJ_LDS"] = lds
+        b = C.c_ulonglong(0)
+        return H.spl_traj_mode(n, nR, nZ, C.byref(b)), b.value
+    finally:
+        if old is None:
+            os.environ.pop("TORJ_TRAJ_LDS", None)
+        else:
+            os.environ["TORJ_TRAJ_LDS"] = old
+
+
+def test_trajectory_kernel_in_the_plan(H):
+    """TORJ_TRAJ_LDS picks the trajectory kernel (split_traj_mode): the cell tile by
+    default, and with 1 the whole-grid LDS kernel only while 48 B for each of the
+    (nR + 2)(nZ + 2) coefficients fit 160 KiB -- the 56 x 56 grid (161 472 B) and the
+    40 x 61 grid of tests/shaped_eq.py (127 008 B) do, 57 x 57 (167 088 B) and 129 x 129
+    do not and fall back to the L2 kernel."""
+    import shaped_eq as E
+
+    assert traj_mode(H, 187, 56, 56, None)[0] == 3
+    for lds in ("0", "2", "3"):
+        assert traj_mode(H, 187, E.NR, E.NZ, lds) == (int(lds), 42 * 63 * 48)
+    assert traj_mode(H, 187, E.NR, E.NZ, "1") == (1, 127008)
+    assert traj_mode(H, 100203, 56, 56, "1") == (1, 58 * 58 * 48)
+    assert 58 * 58 * 48 <= 160 * 1024 < 59 * 59 * 48
+    assert traj_mode(H, 187, 57, 57, "1") == (0, 59 * 59 * 48)
+    assert traj_mode(H, 187, 129, 129, "1")[0] == 0
+    assert traj_mode(H, 187, 129, 129, "3")[0] == 3
 
 
 def plan(H, n, env=None, abs_model=1, counted=0, depo=2, walk=1, negl_skip=1, n_steps=2000, chunk=20,

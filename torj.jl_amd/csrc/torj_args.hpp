@@ -160,6 +160,11 @@ constexpr int kTileNodes = TORJ_TILE_NODES;
 #endif
 constexpr int kTileCells = TORJ_TILE_CELLS;
 
+// where the trajectory kernel reads the field coefficients (torj_k_traj.hpp), and
+// the doubles per node of k_traj_lds' whole-grid table
+enum { kTrajL2 = 0, kTrajLds = 1, kTrajTile = 2, kTrajCell = 3 };
+constexpr int kTrajLdsNS = 6;
+
 #ifndef TORJ_TRAJ_LDS_WAVES
 #define TORJ_TRAJ_LDS_WAVES 1
 #endif

@@ -98,11 +98,22 @@ TORJ_HD int first_point(const double *coef, const Grid &g, double psi_max, const
         }
     }
     const double t = (fabs(ga) <= fabs(gb)) ? a : b;
+    const double p0[3] = {pp[0], pp[1], pp[2]};
     for (int k = 0; k < 3; k++) pp[k] += t * N0[k];
     const double psi_ref = psi_at(coef, g, pp);
     if (!(fabs(psi_ref - psi_max) < 1e-6)) return ST_ENTRY_FAIL;  // :32
-    if (psi_ref > psi_max)                                        // :33-36
+    if (psi_ref > psi_max) {                                      // :33-36
         for (int k = 0; k < 3; k++) pp[k] += 2.0 * (psi_ref - psi_max) * N0[k];
+        // The reference bisects to xtol = 1e-6, so its step above is worth ~1e-6 of
+        // psi.  Bisected to machine precision, psi_ref - psi_max can be one rounding
+        // error and the step less than an ulp of the coordinates: psi stays above
+        // psi_max and make_ray's :138 would refuse a sound ray, on some toroidal
+        // angles and not on others.  The bracket's other end, where g < 0, is then
+        // the entry point (every ray the step does carry inside keeps its bits).
+        const double t_in = ga < 0 ? a : b;
+        if ((ga < 0 || gb < 0) && psi_at(coef, g, pp) > psi_max)
+            for (int k = 0; k < 3; k++) pp[k] = p0[k] + t_in * N0[k];
+    }
     for (int k = 0; k < 3; k++) out[k] = pp[k];
     return ST_OK;
 }

@@ -173,8 +173,7 @@ __device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
 //              cell's bicubic in power form (torj_math.hpp cell_sums: 28 fma per
 //              field with its gradient against the node stencil's 44, no basis
 //              weights); the same fallback to the global cell table.
-enum { kTrajL2 = 0, kTrajLds = 1, kTrajTile = 2, kTrajCell = 3 };
-constexpr int kTrajLdsNS = 6;
+// (the enum and kTrajLdsNS: torj_args.hpp; the choice: torj_split.hpp split_traj_mode)
 static_assert(kTrajLdsNS == kTileNS, "LDS layouts");
 
 __device__ __forceinline__ double wave_min(double v) {

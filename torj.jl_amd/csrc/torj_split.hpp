@@ -48,6 +48,8 @@ struct SplitPlan {
     bool zflag_on, gflag_on, dstream, serial;
     int dstream_env, depo_lag, lds_env, tile_cap, nan_step, zflag_nan_from, defer_lrm, zlatch;
     double tile_margin;
+    int traj_mode;          // the trajectory kernel of this call (kTrajL2 .. kTrajCell)
+    size_t traj_lds_bytes;  // k_traj_lds' dynamic LDS: the whole grid's node table
 
     int block_k0(int b) const { return (int)(first ? (b == 0 ? 0 : first + (long)(b - 1) * kb) : b * kb); }
     int block_len(int b) const { return (int)std::min<long>(first && b == 0 ? first : kb, n_steps - block_k0(b)); }
@@ -56,6 +58,17 @@ struct SplitPlan {
         return (int)(first ? (bw == 0 ? first : first + (long)bw * kb) : std::min<long>((long)(bw + 1) * kb, n_steps));
     }
 };
+
+// The trajectory kernel TORJ_TRAJ_LDS = lds_env selects on an nR x nZ grid: 3 the
+// cell tile, 2 the node tile, 1 the whole-grid table in LDS while it fits 160 KiB
+// (lds_bytes: kTrajLdsNS fp64 for each of the (nR + 2)(nZ + 2) coefficients), and
+// otherwise -- 1 on a larger grid included -- the L2 kernel
+static int split_traj_mode(int lds_env, int nR, int nZ, size_t *lds_bytes) {
+    *lds_bytes = (size_t)(nR + 2) * (nZ + 2) * kTrajLdsNS * sizeof(double);
+    if (lds_env == 3) return kTrajCell;
+    if (lds_env == 2) return kTrajTile;
+    return lds_env == 1 && *lds_bytes <= 160 * 1024 ? kTrajLds : kTrajL2;
+}
 
 // walk: the reference profile's walk can be streamed behind the scans (fa and dso given);
 // negl_skip: the Gauss-Legendre table's early settle is on (GLTable::negl_skip);
@@ -146,6 +159,7 @@ static void split_plan_sizes(SplitPlan &pl, int sched_mode, int sched_waves, siz
     const int tile_max = pl.lds_env == 3 ? kTileCells : kTileNodes;  // cells / nodes
     pl.tile_cap = std::min(tile_max, env_int("TORJ_TILE_CAP", tile_max));
     pl.tile_margin = env_double("TORJ_TILE_MARGIN", 1.001);
+    pl.traj_mode = split_traj_mode(pl.lds_env, a.g.nR, a.g.nZ, &pl.traj_lds_bytes);
     // test hook only (tests/test_gpu_split.py): the scan reads alpha as NaN at
     // this step for every third ray -- a stray setting corrupts results, so say so
     pl.nan_step = env_int("TORJ_TEST_NAN_ALPHA_STEP", -1);
@@ -286,10 +300,10 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
     if (fa && fit_zero(*fa, s3)) return -1;
     const size_t fit_lds = fa ? fit_grid_lds(fa->n_psi) : 0;
     const int G = (int)((n + 63) / 64);
-    const size_t lds_bytes = (size_t)(a.g.nR + 2) * (a.g.nZ + 2) * kTrajLdsNS * sizeof(double);
-    const bool lds_traj = pl.lds_env == 1 && lds_bytes <= 160 * 1024;
-    const bool tile_traj = pl.lds_env == 2, cell_traj = pl.lds_env == 3;
-    sp.traj_mode = cell_traj ? kTrajCell : tile_traj ? kTrajTile : lds_traj ? kTrajLds : kTrajL2;
+    const size_t lds_bytes = pl.traj_lds_bytes;
+    const bool lds_traj = pl.traj_mode == kTrajLds;
+    const bool tile_traj = pl.traj_mode == kTrajTile, cell_traj = pl.traj_mode == kTrajCell;
+    sp.traj_mode = pl.traj_mode;
     const int wpb = std::min(8, std::max(1, (G + p->n_cu - 1) / p->n_cu));
     const int n_blocks = pl.n_blk;
     // one window of the streamed walk, its elimination and its walk as two
