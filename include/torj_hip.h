@@ -42,7 +42,10 @@ extern "C" {
                                torj_ray_entry_beams_gpu, torj_ray_entry_beams_device;
                                still 8 (four more symbols, nothing changed):
                                torj_trace_beams_plasmas, torj_trace_beams_plasmas_device,
-                               torj_ray_entry_beams_plasmas_gpu, torj_ray_entry_beams_plasmas_device */
+                               torj_ray_entry_beams_plasmas_gpu, torj_ray_entry_beams_plasmas_device;
+                               still 8 (four more symbols, nothing changed): torj_plasma_update,
+                               torj_plasma_update_from_coefs, torj_plasma_update_profiles,
+                               torj_plasma_get_cell_table */
 
 /* per-ray status codes (replace the reference's @assert / unhandled returns) */
 enum torj_status {
@@ -103,6 +106,68 @@ int torj_plasma_get_coefs(torj_plasma_t p, int field, double *out);
 double torj_plasma_psi_prof_max(torj_plasma_t p);
 /* plasma.volume_psi_spline at n points (host) */
 int torj_plasma_volume(torj_plasma_t p, int n, const double *psi, double *vol);
+
+/* ---- a live handle's physics replaced in place ------------------------------
+ * A transport loop or a pool of time slices keeps its handles: their workspaces,
+ * streams, events, replicas and communicators, scheduling and timing settings all
+ * stay, and only the equilibrium and the kinetic profiles change.  The grid SIZE
+ * (nR, nZ) is the handle's; the box (the ends of R_coords / Z_coords, or R1 .. Zn),
+ * psi_prof_max and the volume spline follow the new arguments.
+ *
+ * The host arrays are consumed before the call returns, and the new host state is
+ * built by the functions torj_plasma_create[_from_coefs] use, so
+ * torj_plasma_get_coefs and every host entry give bit for bit what a fresh handle
+ * gives.  Every argument is checked, and the new state is complete, before the
+ * handle is touched: a refused call (NULL handle or pointer, n_prof < 2, n_eq < 2,
+ * n_vol < 2; the message names the argument) leaves the handle as it was.
+ *
+ * Before the handle's first GPU use the update is host-only.  Afterwards the new
+ * coefficients are copied to the device and the per-cell power table of the split
+ * pipeline's trajectory kernels is rebuilt from them there (k_cell_table), both
+ * enqueued on `stream` without any synchronisation: traces enqueued earlier on the
+ * stream finish on the old plasma, traces enqueued later see the new one.  `stream`
+ * is the handle's one stream (as torj_trace_device_ex: one stream per handle at a
+ * time; NULL is the legacy default stream, joined the same way); the handle's own
+ * stream, on which the host-pointer entries run, waits for the update on the
+ * device.  Replicas made by torj_trace_beam[_device] get the same update, each on
+ * its own device and stream.  A handle that another handle's
+ * torj_trace_beams_plasmas_device launch lists falls under that call's lifetime
+ * rule: updating it before that launch has been checked (torj_trace_check) is a
+ * caller error.
+ *
+ * Rounding: a handle's first GPU use builds the cell table on the host in long
+ * double; an update rebuilds it on the device in double-double arithmetic (each
+ * entry rounded once from >= 100 bits, the more accurate of the two).  Only the
+ * split pipeline reads the table, so split-pipeline traces of an updated handle
+ * agree with a fresh handle's to rounding (~1e-15 in x and N), and every other
+ * result (one-shot, work-queue, adaptive and multi-beam traces, ray entry, point
+ * evaluations) is bit-identical. */
+/* the arguments of torj_plasma_create without nR, nZ, device, out */
+int torj_plasma_update(torj_plasma_t p, const double *R_coords, const double *Z_coords,
+                       const double *psi_norm_data, int n_prof, const double *psi_prof,
+                       const double *ne_prof, const double *Te_prof, const double *Br_data,
+                       const double *Bz_data, const double *Bphi_data, int n_eq,
+                       const double *eqt1d_psi_norm, const double *eqt1d_volume, void *stream);
+/* the arguments of torj_plasma_create_from_coefs without nR, nZ, device, out.  The
+ * handle keeps no node data afterwards: torj_plasma_update_profiles is refused. */
+int torj_plasma_update_from_coefs(torj_plasma_t p, double R1, double Rn, double Z1, double Zn,
+                                  const double *coef_psi, const double *coef_lnne,
+                                  const double *coef_lnTe, const double *coef_Br,
+                                  const double *coef_Bz, const double *coef_Bphi, int n_vol,
+                                  double vol_psi1, double vol_psin, const double *vol_coefs,
+                                  double psi_prof_max, void *stream);
+/* new kinetic profiles on the handle's equilibrium: make_2d_prof_spline
+ * (src/plasma.jl:16-22) on the psi_norm_data that torj_plasma_create or
+ * torj_plasma_update last gave (the handle keeps a host copy).  Only the ln ne and
+ * ln Te coefficients and psi_prof_max change.  Refused on a handle whose
+ * equilibrium came as coefficients. */
+int torj_plasma_update_profiles(torj_plasma_t p, int n_prof, const double *psi_prof,
+                                const double *ne_prof, const double *Te_prof, void *stream);
+/* the per-cell power table as it stands on the device: (nR-1) x (nZ-1) cells, R
+ * fastest, 96 doubles each (field slot f of Br, Bphi, Bz, ln ne, ln Te, psi at
+ * f * 16, the coefficient of sZ^j sR^i at j * 4 + i, per metre).  Waits for the
+ * handle's stream.  An error before the handle's first GPU use. */
+int torj_plasma_get_cell_table(torj_plasma_t p, double *out);
 
 /* ---- point evaluations (GPU; mirror the reference's unit-tested functions) -- */
 /* Per point i (x, N component-major 3 x n), out is 13 x n component-major:

@@ -10,6 +10,7 @@
 //   torj_k_points.hpp   ray entry and the batched point evaluations
 //   torj_k_beams.hpp    the multi-beam forms of k_trace and the kernels around it,
 //                       also for beams that go through differing plasmas
+//   torj_celltab.hpp    the cell table rebuilt on the device (torj_plasma_update*)
 //   torj_host_util.hpp  fail / HIPCK, the environment knobs, GrowBuf
 //   torj_plasma.hpp     the plasma handle and its device state
 //   torj_fan.hpp        quadrature nodes and the launch fan
@@ -46,6 +47,7 @@ using namespace torj;
 #include "torj_k_depo.hpp"
 #include "torj_k_points.hpp"
 #include "torj_k_beams.hpp"
+#include "torj_celltab.hpp"
 #include "torj_plasma.hpp"
 #include "torj_fan.hpp"
 #include "torj_split.hpp"
@@ -207,33 +209,37 @@ int torj_abs_al_init(int n) {
     return 0;
 }
 
-int torj_plasma_create(int nR, int nZ, const double *R, const double *Z, const double *psi_norm,
-                       int n_prof, const double *psi_prof, const double *ne_prof,
-                       const double *Te_prof, const double *Br, const double *Bz,
-                       const double *Bphi, int n_eq, const double *eq_psi, const double *eq_vol,
-                       int device, torj_plasma_t *out) {
-    if (!out) return fail("out is NULL");
-    if (nR < 2 || nZ < 2 || n_prof < 2 || n_eq < 2) return fail("Plasma: grids need >= 2 points");
-    const size_t nd = (size_t)nR * nZ, nc = (size_t)(nR + 2) * (nZ + 2);
+}  // extern "C"
+
+// make_2d_prof_spline (src/plasma.jl:16-22): a 1-D profile over psi, resampled on the uniform
+// range and taken to its logarithm, mapped through the nodes' psi_norm -> 2-D coefficients
+static void prof2d_coefs(int nR, int nZ, const double *psi_norm, int n_prof, const double *psi_prof,
+                         const double *prof, std::vector<double> &c2) {
+    const size_t nd = (size_t)nR * nZ;
+    std::vector<double> pr = uniform_range(psi_prof[0], psi_prof[n_prof - 1], n_prof);
+    std::vector<double> p2(n_prof), c1(n_prof + 2), d2(nd);
+    natcubic(n_prof, psi_prof, prof, n_prof, pr.data(), p2.data());
+    for (double &v : p2) v = std::log(v);
+    bspl1d_prefilter(n_prof, p2.data(), 1, c1.data(), 1);
+    for (size_t k = 0; k < nd; k++)
+        d2[k] = bspl1d_eval(c1, n_prof, psi_prof[0], psi_prof[n_prof - 1], psi_norm[k]);
+    bspl2d_prefilter(nR, nZ, d2.data(), c2.data());
+}
+
+// The host state of a plasma from its node data, into the blank handle p: the body of
+// torj_plasma_create, and of torj_plasma_update on a scratch handle (plasma_adopt)
+static int plasma_from_maps(torj_plasma_s *p, int nR, int nZ, const double *R, const double *Z,
+                            const double *psi_norm, int n_prof, const double *psi_prof, const double *ne_prof,
+                            const double *Te_prof, const double *Br, const double *Bz, const double *Bphi,
+                            int n_eq, const double *eq_psi, const double *eq_vol, int device) {
+    const size_t nc = (size_t)(nR + 2) * (nZ + 2);
     std::vector<double> cpsi(nc), cne(nc), cte(nc), cbr(nc), cbz(nc), cbp(nc);
     bspl2d_prefilter(nR, nZ, psi_norm, cpsi.data());
     bspl2d_prefilter(nR, nZ, Br, cbr.data());
     bspl2d_prefilter(nR, nZ, Bz, cbz.data());
     bspl2d_prefilter(nR, nZ, Bphi, cbp.data());
-    // make_2d_prof_spline (src/plasma.jl:16-22)
-    auto prof2d = [&](const double *prof, std::vector<double> &c2) {
-        std::vector<double> pr = uniform_range(psi_prof[0], psi_prof[n_prof - 1], n_prof);
-        std::vector<double> p2(n_prof), c1(n_prof + 2), d2(nd);
-        natcubic(n_prof, psi_prof, prof, n_prof, pr.data(), p2.data());
-        for (double &v : p2) v = std::log(v);
-        bspl1d_prefilter(n_prof, p2.data(), 1, c1.data(), 1);
-        for (size_t k = 0; k < nd; k++)
-            d2[k] = bspl1d_eval(c1, n_prof, psi_prof[0], psi_prof[n_prof - 1], psi_norm[k]);
-        bspl2d_prefilter(nR, nZ, d2.data(), c2.data());
-    };
-    prof2d(ne_prof, cne);
-    prof2d(Te_prof, cte);
-    auto *p = new torj_plasma_s();
+    prof2d_coefs(nR, nZ, psi_norm, n_prof, psi_prof, ne_prof, cne);
+    prof2d_coefs(nR, nZ, psi_norm, n_prof, psi_prof, Te_prof, cte);
     // volume_psi_spline (src/plasma.jl:42-44)
     std::vector<double> pr = uniform_range(eq_psi[0], eq_psi[n_eq - 1], n_eq), v2(n_eq);
     natcubic(n_eq, eq_psi, eq_vol, n_eq, pr.data(), v2.data());
@@ -243,9 +249,101 @@ int torj_plasma_create(int nR, int nZ, const double *R, const double *Z, const d
     p->vol_coef.assign(n_eq + 2, 0.0);
     bspl1d_prefilter(n_eq, v2.data(), 1, p->vol_coef.data(), 1);
     p->psi_prof_max = *std::max_element(psi_prof, psi_prof + n_prof);
+    p->psi_nodes.assign(psi_norm, psi_norm + (size_t)nR * nZ);
     const double *fields[6] = {cpsi.data(), cne.data(), cte.data(), cbr.data(), cbz.data(), cbp.data()};
-    const int rc = plasma_finish(p, nR, nZ, R[0], R[nR - 1], Z[0], Z[nZ - 1], fields, device, out);
-    if (rc) delete p;
+    torj_plasma_t out;
+    return plasma_finish(p, nR, nZ, R[0], R[nR - 1], Z[0], Z[nZ - 1], fields, device, &out);
+}
+
+// ... and from Interpolations.jl coefficients (torj_plasma_create_from_coefs, torj_plasma_update_from_coefs)
+static int plasma_from_coefs(torj_plasma_s *p, int nR, int nZ, double R1, double Rn, double Z1, double Zn,
+                             const double *c_psi, const double *c_lnne, const double *c_lnTe, const double *c_Br,
+                             const double *c_Bz, const double *c_Bphi, int n_vol, double vol_psi1,
+                             double vol_psin, const double *vol_coefs, double psi_prof_max, int device) {
+    p->n_vol = n_vol;
+    p->v1 = vol_psi1;
+    p->vn = vol_psin;
+    p->vol_coef.assign(vol_coefs, vol_coefs + n_vol + 2);
+    p->psi_prof_max = psi_prof_max;
+    const double *fields[6] = {c_psi, c_lnne, c_lnTe, c_Br, c_Bz, c_Bphi};
+    torj_plasma_t out;
+    return plasma_finish(p, nR, nZ, R1, Rn, Z1, Zn, fields, device, &out);
+}
+
+// ===========================================================================
+// torj_plasma_update*: a live handle's physics replaced
+// ===========================================================================
+// the device half, on one handle or replica whose device state exists: the new
+// coefficients into d_coef (from pageable memory, consumed when the copy returns:
+// beams_upload's rule), then d_cellp rebuilt from them, both in `s`'s order
+static int plasma_update_enqueue(torj_plasma_s *q, hipStream_t s) {
+    HIPCK(hipMemcpyAsync(q->d_coef, q->coef.data(), q->coef.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    const long n = (long)(q->g.nR - 1) * (q->g.nZ - 1) * kCellNS;
+    hipLaunchKernelGGL(k_cell_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q->d_coef, q->g, q->d_cellp);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+// The complete new host state in `fresh` (a scratch handle, the same grid size) becomes p's and
+// its replicas'; where device state exists the device half follows: the handle's on the caller's
+// stream (NULL: on_caller_stream's fork and join), each replica's on its own device and stream.
+// Nothing waits for the device.
+static int plasma_adopt(torj_plasma_s *p, torj_plasma_s &fresh, void *stream) {
+    std::vector<torj_plasma_s *> live;  // handles whose device state exists
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        for (size_t k = 0; k < std::max<size_t>(1, p->replicas.size()); k++) {
+            torj_plasma_s *q = k == 0 ? p : p->replicas[k];
+            q->g = fresh.g;
+            q->coef = fresh.coef;
+            q->n_vol = fresh.n_vol, q->v1 = fresh.v1, q->vn = fresh.vn;
+            q->vol_coef = fresh.vol_coef;
+            q->psi_prof_max = fresh.psi_prof_max;
+            if (q->d_flags) live.push_back(q);
+        }
+        p->psi_nodes.swap(fresh.psi_nodes);
+    }
+    int rc = 0;
+    for (torj_plasma_s *q : live) {
+        if (hipSetDevice(q->device) != hipSuccess) {
+            rc = fail("hipSetDevice(%d) failed", q->device);
+            break;
+        }
+        if (q != p) {
+            rc = plasma_update_enqueue(q, q->stream);
+        } else {
+            rc = on_caller_stream(p, stream, [&](hipStream_t s) {
+                if (plasma_update_enqueue(p, s)) return -1;
+                if (s == p->stream) return 0;
+                // the host-pointer entries run on the handle's own stream: it waits for this update
+                if (!p->ev_U) HIPCK(hipEventCreateWithFlags(&p->ev_U, hipEventDisableTiming));
+                HIPCK(hipEventRecord(p->ev_U, s));
+                HIPCK(hipStreamWaitEvent(p->stream, p->ev_U, 0));
+                return 0;
+            });
+        }
+        if (rc) break;
+    }
+    if (live.size() > 1 || (live.size() == 1 && live[0] != p)) (void)hipSetDevice(p->device);
+    return rc;
+}
+
+extern "C" {
+
+int torj_plasma_create(int nR, int nZ, const double *R, const double *Z, const double *psi_norm,
+                       int n_prof, const double *psi_prof, const double *ne_prof,
+                       const double *Te_prof, const double *Br, const double *Bz,
+                       const double *Bphi, int n_eq, const double *eq_psi, const double *eq_vol,
+                       int device, torj_plasma_t *out) {
+    if (!out) return fail("out is NULL");
+    if (nR < 2 || nZ < 2 || n_prof < 2 || n_eq < 2) return fail("Plasma: grids need >= 2 points");
+    auto *p = new torj_plasma_s();
+    const int rc = plasma_from_maps(p, nR, nZ, R, Z, psi_norm, n_prof, psi_prof, ne_prof, Te_prof, Br, Bz, Bphi,
+                                    n_eq, eq_psi, eq_vol, device);
+    if (rc)
+        delete p;
+    else
+        *out = p;
     return rc;
 }
 
@@ -258,15 +356,102 @@ int torj_plasma_create_from_coefs(int nR, int nZ, double R1, double Rn, double Z
     if (!out) return fail("out is NULL");
     if (nR < 2 || nZ < 2 || n_vol < 2) return fail("Plasma: grids need >= 2 points");
     auto *p = new torj_plasma_s();
-    p->n_vol = n_vol;
-    p->v1 = vol_psi1;
-    p->vn = vol_psin;
-    p->vol_coef.assign(vol_coefs, vol_coefs + n_vol + 2);
-    p->psi_prof_max = psi_prof_max;
-    const double *fields[6] = {c_psi, c_lnne, c_lnTe, c_Br, c_Bz, c_Bphi};
-    const int rc = plasma_finish(p, nR, nZ, R1, Rn, Z1, Zn, fields, device, out);
-    if (rc) delete p;
+    const int rc = plasma_from_coefs(p, nR, nZ, R1, Rn, Z1, Zn, c_psi, c_lnne, c_lnTe, c_Br, c_Bz, c_Bphi, n_vol,
+                                     vol_psi1, vol_psin, vol_coefs, psi_prof_max, device);
+    if (rc)
+        delete p;
+    else
+        *out = p;
     return rc;
+}
+
+// every refusal before the handle is touched; the new state whole in a scratch handle, then adopted
+int torj_plasma_update(torj_plasma_t p, const double *R, const double *Z, const double *psi_norm, int n_prof,
+                       const double *psi_prof, const double *ne_prof, const double *Te_prof, const double *Br,
+                       const double *Bz, const double *Bphi, int n_eq, const double *eq_psi,
+                       const double *eq_vol, void *stream) {
+    if (!p) return fail("torj_plasma_update: p is NULL");
+    const struct {
+        const char *name;
+        const void *ptr;
+    } args[] = {{"R_coords", R},     {"Z_coords", Z},   {"psi_norm_data", psi_norm}, {"psi_prof", psi_prof},
+                {"ne_prof", ne_prof}, {"Te_prof", Te_prof}, {"Br_data", Br},          {"Bz_data", Bz},
+                {"Bphi_data", Bphi}, {"eqt1d_psi_norm", eq_psi}, {"eqt1d_volume", eq_vol}};
+    for (const auto &a : args)
+        if (!a.ptr) return fail("torj_plasma_update: %s is NULL", a.name);
+    if (n_prof < 2) return fail("torj_plasma_update: n_prof = %d < 2", n_prof);
+    if (n_eq < 2) return fail("torj_plasma_update: n_eq = %d < 2", n_eq);
+    torj_plasma_s fresh;
+    if (plasma_from_maps(&fresh, p->g.nR, p->g.nZ, R, Z, psi_norm, n_prof, psi_prof, ne_prof, Te_prof, Br, Bz, Bphi,
+                         n_eq, eq_psi, eq_vol, p->device))
+        return -1;
+    return plasma_adopt(p, fresh, stream);
+}
+
+int torj_plasma_update_from_coefs(torj_plasma_t p, double R1, double Rn, double Z1, double Zn,
+                                  const double *c_psi, const double *c_lnne, const double *c_lnTe,
+                                  const double *c_Br, const double *c_Bz, const double *c_Bphi, int n_vol,
+                                  double vol_psi1, double vol_psin, const double *vol_coefs, double psi_prof_max,
+                                  void *stream) {
+    if (!p) return fail("torj_plasma_update_from_coefs: p is NULL");
+    const struct {
+        const char *name;
+        const void *ptr;
+    } args[] = {{"coef_psi", c_psi}, {"coef_lnne", c_lnne}, {"coef_lnTe", c_lnTe}, {"coef_Br", c_Br},
+                {"coef_Bz", c_Bz},   {"coef_Bphi", c_Bphi}, {"vol_coefs", vol_coefs}};
+    for (const auto &a : args)
+        if (!a.ptr) return fail("torj_plasma_update_from_coefs: %s is NULL", a.name);
+    if (n_vol < 2) return fail("torj_plasma_update_from_coefs: n_vol = %d < 2", n_vol);
+    torj_plasma_s fresh;  // (no node data: a later profiles-only update is refused)
+    if (plasma_from_coefs(&fresh, p->g.nR, p->g.nZ, R1, Rn, Z1, Zn, c_psi, c_lnne, c_lnTe, c_Br, c_Bz, c_Bphi,
+                          n_vol, vol_psi1, vol_psin, vol_coefs, psi_prof_max, p->device))
+        return -1;
+    return plasma_adopt(p, fresh, stream);
+}
+
+int torj_plasma_update_profiles(torj_plasma_t p, int n_prof, const double *psi_prof, const double *ne_prof,
+                                const double *Te_prof, void *stream) {
+    if (!p) return fail("torj_plasma_update_profiles: p is NULL");
+    if (!psi_prof) return fail("torj_plasma_update_profiles: psi_prof is NULL");
+    if (!ne_prof) return fail("torj_plasma_update_profiles: ne_prof is NULL");
+    if (!Te_prof) return fail("torj_plasma_update_profiles: Te_prof is NULL");
+    if (n_prof < 2) return fail("torj_plasma_update_profiles: n_prof = %d < 2", n_prof);
+    const int nR = p->g.nR, nZ = p->g.nZ;
+    torj_plasma_s fresh;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->psi_nodes.empty())
+            return fail("torj_plasma_update_profiles: the handle has no psi_norm_data (its equilibrium came as "
+                        "coefficients: torj_plasma_create_from_coefs / torj_plasma_update_from_coefs); use "
+                        "torj_plasma_update_from_coefs");
+        fresh.g = p->g;
+        fresh.coef = p->coef;
+        fresh.n_vol = p->n_vol, fresh.v1 = p->v1, fresh.vn = p->vn;
+        fresh.vol_coef = p->vol_coef;
+        fresh.psi_nodes = p->psi_nodes;
+    }
+    // the ln ne and ln Te slots alone; the equilibrium's four stay as they are
+    const size_t nc = (size_t)(nR + 2) * (nZ + 2);
+    std::vector<double> c2(nc);
+    const double *prof[2] = {ne_prof, Te_prof};
+    const int slot[2] = {F_LNNE, F_LNTE};
+    for (int f = 0; f < 2; f++) {
+        prof2d_coefs(nR, nZ, fresh.psi_nodes.data(), n_prof, psi_prof, prof[f], c2);
+        for (size_t k = 0; k < nc; k++) fresh.coef[k * kNF + slot[f]] = c2[k];
+    }
+    fresh.psi_prof_max = *std::max_element(psi_prof, psi_prof + n_prof);
+    return plasma_adopt(p, fresh, stream);
+}
+
+int torj_plasma_get_cell_table(torj_plasma_t p, double *out) {
+    if (!p) return fail("torj_plasma_get_cell_table: p is NULL");
+    if (!out) return fail("torj_plasma_get_cell_table: out is NULL");
+    if (!p->d_flags) return fail("torj_plasma_get_cell_table: the handle has no device state yet (no GPU use so far)");
+    HIPCK(hipSetDevice(p->device));
+    HIPCK(hipStreamSynchronize(p->stream));
+    HIPCK(hipMemcpy(out, p->d_cellp, (size_t)(p->g.nR - 1) * (p->g.nZ - 1) * kCellRec * sizeof(double),
+                    hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int torj_plasma_destroy(torj_plasma_t p) {
@@ -293,6 +478,7 @@ int torj_plasma_destroy(torj_plasma_t p) {
     if (p->stream) (void)hipStreamDestroy(p->stream);
     if (p->ev_Nin) (void)hipEventDestroy(p->ev_Nin);
     if (p->ev_Nout) (void)hipEventDestroy(p->ev_Nout);
+    if (p->ev_U) (void)hipEventDestroy(p->ev_U);
     if (p->sched.d) (void)hipFree(p->sched.d);
     if (p->fit.d) (void)hipFree(p->fit.d);
     if (p->d_flags) (void)hipFree(p->d_flags);

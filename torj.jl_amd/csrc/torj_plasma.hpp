@@ -126,6 +126,10 @@ struct torj_plasma_s {
     int device = 0;
     Grid g{};
     std::vector<double> coef;  // interleaved host copy
+    // the psi_norm_data (nR x nZ, R fastest) torj_plasma_create / torj_plasma_update last
+    // gave: torj_plasma_update_profiles maps new profiles through it (empty on a handle
+    // whose equilibrium came as coefficients)
+    std::vector<double> psi_nodes;
     double *d_coef = nullptr;
     double *d_cellp = nullptr;  // per-cell power form of coef (the cell-tiled trajectory kernel)
     int n_vol = 0;
@@ -181,6 +185,7 @@ struct torj_plasma_s {
     hipEvent_t ev_T[kRing] = {}, ev_A[kRing] = {}, ev_S[kRing] = {}, ev_J = nullptr, ev_F = nullptr;
     hipEvent_t ev_D = nullptr;
     hipEvent_t ev_Nin = nullptr, ev_Nout = nullptr;  // a NULL caller stream's fork / join
+    hipEvent_t ev_U = nullptr;  // torj_plasma_update on a caller's stream: the handle's own stream waits for it
 };
 
 static const int kFieldSlot[6] = {F_PSI, F_LNNE, F_LNTE, F_BR, F_BZ, F_BPHI};

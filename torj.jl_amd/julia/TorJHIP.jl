@@ -52,8 +52,10 @@ abs_Al_init(n::Integer) = check(ccall((:torj_abs_al_init, libtorj), Cint, (Cint,
 mutable struct GPUPlasma
     h::Ptr{Cvoid}
     psi_prof_max::Float64
-    function GPUPlasma(h::Ptr{Cvoid}, psi_prof_max::Float64)
-        p = new(h, psi_prof_max)
+    nR::Int                  # the handle's grid size (update! keeps it)
+    nZ::Int
+    function GPUPlasma(h::Ptr{Cvoid}, psi_prof_max::Float64, nR::Integer, nZ::Integer)
+        p = new(h, psi_prof_max, nR, nZ)
         finalizer(x -> ccall((:torj_plasma_destroy, libtorj), Cint, (Ptr{Cvoid},), x.h), p)
         return p
     end
@@ -73,7 +75,7 @@ function GPUPlasma(R::Vector{Float64}, Z::Vector{Float64}, psi_norm::Matrix{Floa
                  Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Ptr{Cvoid}}),
                 length(R), length(Z), R, Z, psi_norm, length(psi_prof), psi_prof, ne, Te,
                 Br, Bz, Bphi, length(eq_psi), eq_psi, eq_vol, device, h))
-    return GPUPlasma(h[], maximum(psi_prof))
+    return GPUPlasma(h[], maximum(psi_prof), length(R), length(Z))
 end
 
 # Interpolations.jl: cubic_spline_interpolation(ranges, A; extrapolation_bc=Line())
@@ -103,7 +105,32 @@ function GPUPlasma(p::TorJ.Plasma; device::Integer=0)
                 length(rR), length(rZ), first(rR), last(rR), first(rZ), last(rZ), c[1], c[2],
                 c[3], c[4], c[5], c[6], length(rv), first(rv), last(rv), cv,
                 Float64(p.psi_prof_max), device, h))
-    return GPUPlasma(h[], Float64(p.psi_prof_max))
+    return GPUPlasma(h[], Float64(p.psi_prof_max), length(rR), length(rZ))
+end
+
+"""update!(h, plasma::TorJ.Plasma; stream=C_NULL) -- the live handle `h` takes `plasma`'s
+splines (torj_plasma_update_from_coefs): a transport loop keeps one handle, with its
+workspaces, streams and replicas, and refills it between traces.  The (R, Z) grid must have
+the size `h` was built with; its ranges may differ.  After the handle's first GPU use the
+copy and the rebuild of the cell table are enqueued on `stream` without synchronisation."""
+function update!(h::GPUPlasma, p::TorJ.Plasma; stream::Ptr{Cvoid}=C_NULL)
+    rR, rZ = _ranges(p.psi_norm_spline)
+    c = [_coefs(getfield(p, f)) for f in (:psi_norm_spline, :ne_spline, :Te_spline,
+                                           :Br_spline, :Bz_spline, :Bϕ_spline)]
+    all(size(x) == (length(rR) + 2, length(rZ) + 2) for x in c) ||
+        throw(ArgumentError("TorJ.Plasma splines are not on one (R, Z) grid"))
+    (length(rR), length(rZ)) == (h.nR, h.nZ) ||
+        throw(ArgumentError("update! keeps the handle's grid size $((h.nR, h.nZ)), got $((length(rR), length(rZ)))"))
+    rv = _ranges(p.volume_psi_spline)[1]
+    cv = _coefs(p.volume_psi_spline)
+    check(ccall((:torj_plasma_update_from_coefs, libtorj), Cint,
+                (Ptr{Cvoid}, Float64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Float64, Float64,
+                 Ptr{Float64}, Float64, Ptr{Cvoid}),
+                h.h, first(rR), last(rR), first(rZ), last(rZ), c[1], c[2], c[3], c[4], c[5], c[6],
+                length(rv), first(rv), last(rv), cv, Float64(p.psi_prof_max), stream))
+    h.psi_prof_max = Float64(p.psi_prof_max)
+    return h
 end
 
 # one GPU copy per TorJ.Plasma object (make_ray / make_beam on TorJ's own type)

@@ -67,6 +67,14 @@ _SIGS = {
     "torj_plasma_get_coefs": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "torj_plasma_psi_prof_max": (C.c_double, [C.c_void_p]),
     "torj_plasma_volume": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    # a live handle's physics replaced in place (the creates' arguments, then the stream)
+    "torj_plasma_update": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                     C.c_int, _dp, _dp, C.c_void_p]),
+    "torj_plasma_update_from_coefs": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int,
+                                                C.c_double, C.c_double, _dp, C.c_double, C.c_void_p]),
+    "torj_plasma_update_profiles": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_void_p]),
+    "torj_plasma_get_cell_table": (C.c_int, [C.c_void_p, _dp]),
     "torj_eval_plasma": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp]),
     "torj_dispersion": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp,
                                   _dp]),

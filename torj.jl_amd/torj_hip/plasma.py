@@ -70,6 +70,68 @@ class Plasma:
     def handle(self):
         return self._h
 
+    # ---- the live handle's physics replaced in place (torj_plasma_update*) ----
+    def update(self, R_coords, Z_coords, psi_norm_data, psi_prof, ne_prof, Te_prof, Br_data, Bz_data,
+               Bphi_data, eqt1d_psi_norm, eqt1d_volume, stream=None):
+        """torj_plasma_update: the constructor's arguments on this handle, whose grid
+        size, workspaces, streams, replicas and settings stay.  After the first GPU
+        use the device copy follows in `stream`'s order (an integer stream handle;
+        None: the default stream), without synchronisation; the arrays are consumed
+        when the call returns."""
+        R, Z = f64(R_coords), f64(Z_coords)
+        nR, nZ = len(self.R_coords), len(self.Z_coords)
+        if (len(R), len(Z)) != (nR, nZ):
+            raise ValueError(f"update keeps the grid size {(nR, nZ)}, got {(len(R), len(Z))}")
+
+        def m(a):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (nR, nZ):
+                raise ValueError(f"2-D map has shape {a.shape}, expected {(nR, nZ)}")
+            return np.ascontiguousarray(a.T)  # column-major (R fastest)
+
+        keep = [m(psi_norm_data), f64(psi_prof), f64(ne_prof), f64(Te_prof), m(Br_data),
+                m(Bz_data), m(Bphi_data), f64(eqt1d_psi_norm), f64(eqt1d_volume)]
+        check(lib().torj_plasma_update(self._h, dptr(R), dptr(Z), dptr(keep[0]), len(keep[1]),
+                                       dptr(keep[1]), dptr(keep[2]), dptr(keep[3]), dptr(keep[4]),
+                                       dptr(keep[5]), dptr(keep[6]), len(keep[7]), dptr(keep[7]),
+                                       dptr(keep[8]), stream))
+        self.R_coords, self.Z_coords = R, Z
+        self.psi_prof_max = lib().torj_plasma_psi_prof_max(self._h)
+
+    def update_from_coefs(self, R_range, Z_range, coefs: dict, vol_psi_range, vol_coefs, psi_prof_max,
+                          stream=None):
+        """torj_plasma_update_from_coefs: from_coefs' arguments on this handle."""
+        nR, nZ = len(self.R_coords), len(self.Z_coords)
+        c = {k: np.ascontiguousarray(np.asarray(coefs[k], dtype=np.float64).T) for k in FIELDS}
+        for k in FIELDS:
+            if c[k].shape != (nZ + 2, nR + 2):
+                raise ValueError(f"coefs[{k!r}] has shape {c[k].shape[::-1]}, expected {(nR + 2, nZ + 2)}")
+        vc = f64(vol_coefs)
+        check(lib().torj_plasma_update_from_coefs(
+            self._h, R_range[0], R_range[1], Z_range[0], Z_range[1], *[dptr(c[k]) for k in FIELDS],
+            len(vc) - 2, vol_psi_range[0], vol_psi_range[1], dptr(vc), psi_prof_max, stream))
+        self.R_coords = np.linspace(R_range[0], R_range[1], nR)
+        self.Z_coords = np.linspace(Z_range[0], Z_range[1], nZ)
+        self.psi_prof_max = psi_prof_max
+
+    def update_profiles(self, psi_prof, ne_prof, Te_prof, stream=None):
+        """torj_plasma_update_profiles: new ne / Te profiles on the equilibrium this
+        handle was last given as node data."""
+        pp, ne, te = f64(psi_prof), f64(ne_prof), f64(Te_prof)
+        if not (len(pp) == len(ne) == len(te)):
+            raise ValueError("psi_prof, ne_prof and Te_prof must have one length")
+        check(lib().torj_plasma_update_profiles(self._h, len(pp), dptr(pp), dptr(ne), dptr(te), stream))
+        self.psi_prof_max = lib().torj_plasma_psi_prof_max(self._h)
+
+    def cell_table(self) -> np.ndarray:
+        """torj_plasma_get_cell_table: the per-cell power table on the device,
+        (nZ - 1, nR - 1, 6, 4, 4): cell, field slot (Br, Bphi, Bz, ln ne, ln Te, psi),
+        power of sZ, power of sR."""
+        nR, nZ = len(self.R_coords), len(self.Z_coords)
+        out = np.zeros((nZ - 1, nR - 1, 6, 4, 4))
+        check(lib().torj_plasma_get_cell_table(self._h, dptr(out)))
+        return out
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
