@@ -188,6 +188,34 @@ def test_reference_deposition_in_ray_batches(gpu, T, hplasma):
     assert np.abs(a.dP_shell - b.dP_shell).max() <= 1e-13 * np.abs(a.dP_shell).max()
 
 
+def test_ray_batches_without_optional_arrays(gpu, T, hplasma):
+    """TORJ_SPLIT_BATCH=64 on 150 rays without deposition, weights, launch points
+    and s0 (two 64-ray batches and a partial one, every optional array of the
+    batch loop absent): every per-ray output equals the single launch bit for
+    bit.  As in the test above, only the equality is observed, not the batching."""
+    import os
+
+    _, xp, Np, _, _, om = _fan(T, hplasma, 1, n_rings=14, min_az=5)
+    xp, Np = xp[:150], Np[:150]
+    kw = dict(ds=1e-4, n_steps=300, traj_stride=100)
+    old = os.environ.get("TORJ_SPLIT_BATCH")
+    try:
+        hplasma.set_sched(0)
+        a = T.trace(hplasma, xp, Np, om, 1, **kw)
+        os.environ["TORJ_SPLIT_BATCH"] = "64"
+        b = T.trace(hplasma, xp, Np, om, 1, **kw)
+    finally:
+        hplasma.set_sched(-1)
+        if old is None:
+            os.environ.pop("TORJ_SPLIT_BATCH", None)
+        else:
+            os.environ["TORJ_SPLIT_BATCH"] = old
+    for f in ("state", "status", "steps"):
+        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert np.array_equal(a.traj, b.traj, equal_nan=True)
+    assert not b.P_dep.any() and not b.dP_shell.any()
+
+
 def _oscillating_ray(periods, n=3001, s0=0.05, ds=1e-4, R0=1.7, a=0.6):
     """make_ray-style vectors of a synthetic path in the midplane whose psi goes
     from outside the plasma in to 0.5 and then oscillates about it (the

@@ -202,7 +202,7 @@ static int beam_stage(torj_plasma_s *q, size_t slot, int nslots) {
 
 // One device's share of torj_trace_beam: its shards k0, k0 + dk, ... traced on
 // the replica's stream from compact device buffers, with dP_shell accumulated
-// on the device (d_dP, zeroed here) for the reduce.  Host arrays are the
+// on the device (d_dP, zeroed here) for the reduce.  `host`'s arrays are the
 // caller's (pageable); each shard goes through pinned staging in two slots on
 // a copy stream, pipelined so that shard j + 1's upload and shard j - 1's
 // download overlap shard j's trace:
@@ -214,14 +214,13 @@ static int beam_stage(torj_plasma_s *q, size_t slot, int nslots) {
 // (row r of an array at r * cnt) on both sides, so each transfer is one copy;
 // a slot's input and output blocks sit at fixed offsets (sized for the
 // largest shard), so they never overlap across shards of different sizes.
-static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, int n, int S, int k0, int dk,
-                       const double *x0, const double *N0, const double *w, int n_psi,
-                       const double *grid, const double *xl, const double *s0, double *state,
-                       int *status, int *steps, double *P_dep, double *traj, double *d_dP) {
+static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, const RayIO &host, int S, int k0, int dk,
+                       int n_psi, double *d_dP) {
     if (ensure_device(q)) return -1;
     hipStream_t s = q->stream;
-    const bool depo = n_psi >= 2 && grid;
-    const bool tr_out = traj && cfg->traj_stride > 0 && cfg->n_steps / cfg->traj_stride > 0;
+    const int n = host.n;
+    const bool depo = n_psi >= 2 && host.psi_grid;
+    const bool tr_out = host.traj && cfg->traj_stride > 0 && cfg->n_steps / cfg->traj_stride > 0;
     const int n_save = tr_out ? cfg->n_steps / cfg->traj_stride : 0;
     std::vector<int> los, cnts;  // this device's shards
     int m = 0;
@@ -236,10 +235,10 @@ static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, int n, int S
     if (m == 0) return 0;
     DevBufs B;
     double *dgrid = nullptr;
-    if (depo && B.up(&dgrid, grid, n_psi, s)) return -1;
+    if (depo && B.up(&dgrid, host.psi_grid, n_psi, s)) return -1;
     // rows per shard: inputs x0 N0 [w] [x_launch] [s0]; outputs state [P_dep]
     // [traj], then status and steps (two int rows in one double row)
-    const int n_in = 6 + (w ? 1 : 0) + (xl ? 3 : 0) + (s0 ? 1 : 0);
+    const int n_in = 6 + (host.weights ? 1 : 0) + (host.x_launch ? 3 : 0) + (host.s0 ? 1 : 0);
     const int n_out = 7 + (depo ? 1 : 0) + n_save * 5 + 1;
     const size_t slot = (size_t)(n_in + n_out) * m;
     const int nk = (int)los.size();
@@ -258,9 +257,9 @@ static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, int n, int S
         v.in = c;
         v.x0 = c, c += 3 * (size_t)cnt;
         v.N0 = c, c += 3 * (size_t)cnt;
-        if (w) v.w = c, c += cnt;
-        if (xl) v.xl = c, c += 3 * (size_t)cnt;
-        if (s0) v.s0 = c, c += cnt;
+        if (host.weights) v.w = c, c += cnt;
+        if (host.x_launch) v.xl = c, c += 3 * (size_t)cnt;
+        if (host.s0) v.s0 = c, c += cnt;
         v.n_in = c - v.in;
         // outputs at a fixed offset (m rays' inputs), so a shard's outputs never
         // share bytes with the next shards' inputs in the same slot: shard
@@ -291,8 +290,8 @@ static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, int n, int S
         const int r = j & 1, lo = los[j], cnt = cnts[j];
         if (j >= 2) HIPCK(hipEventSynchronize(bs.up[r]));  // shard j - 2's upload left the slot
         const View h = view(hbase, r, cnt), d = view(dbase, r, cnt);
-        pack(h.x0, x0, 3, lo, cnt), pack(h.N0, N0, 3, lo, cnt), pack(h.w, w, 1, lo, cnt);
-        pack(h.xl, xl, 3, lo, cnt), pack(h.s0, s0, 1, lo, cnt);
+        pack(h.x0, host.x0, 3, lo, cnt), pack(h.N0, host.N0, 3, lo, cnt), pack(h.w, host.weights, 1, lo, cnt);
+        pack(h.xl, host.x_launch, 3, lo, cnt), pack(h.s0, host.s0, 1, lo, cnt);
         HIPCK(hipMemcpyAsync(d.in, h.in, h.n_in * D, hipMemcpyHostToDevice, bs.sc));
         HIPCK(hipEventRecord(bs.up[r], bs.sc));
         return 0;
@@ -301,11 +300,11 @@ static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, int n, int S
         const int r = j & 1, lo = los[j], cnt = cnts[j];
         HIPCK(hipEventSynchronize(bs.dn[r]));
         const View h = view(hbase, r, cnt);
-        unpack(state, h.state, 7, lo, cnt);
-        if (depo) unpack(P_dep, h.Pdep, 1, lo, cnt);
-        if (n_save) unpack(traj, h.traj, n_save * 5, lo, cnt);
-        memcpy(status + lo, h.status, cnt * sizeof(int));
-        memcpy(steps + lo, h.steps, cnt * sizeof(int));
+        unpack(host.state, h.state, 7, lo, cnt);
+        if (depo) unpack(host.P_dep, h.Pdep, 1, lo, cnt);
+        if (n_save) unpack(host.traj, h.traj, n_save * 5, lo, cnt);
+        memcpy(host.status + lo, h.status, cnt * sizeof(int));
+        memcpy(host.steps + lo, h.steps, cnt * sizeof(int));
         return 0;
     };
     // TORJ_BEAM_SYNC=1 (read per call; diagnosis): drain the device after every
@@ -322,10 +321,11 @@ static int beam_worker(torj_plasma_s *q, const torj_trace_cfg *cfg, int n, int S
         const View d = view(dbase, r, cnt);
         HIPCK(hipStreamWaitEvent(s, bs.up[r], 0));
         if (j >= 2) HIPCK(hipStreamWaitEvent(s, bs.dn[r], 0));  // the slot's previous outputs are out
-        if (torj_trace_device_ex(q, cfg, cnt, d.x0, d.N0, d.w, depo ? n_psi : 0, dgrid, d.xl, d.s0,
-                                 d.state, d.status, d.steps, depo ? d_dP : nullptr, d.Pdep, d.traj,
-                                 nullptr, s))
-            return -1;
+        RayIO io{};  // the shard on the device: its slot's arrays (Pdep only with deposition), no counters
+        io.n = cnt, io.x0 = d.x0, io.N0 = d.N0, io.weights = d.w, io.x_launch = d.xl, io.s0 = d.s0;
+        io.state = d.state, io.status = d.status, io.steps = d.steps, io.P_dep = d.Pdep, io.traj = d.traj;
+        io.psi_grid = dgrid, io.dP_shell = depo ? d_dP : nullptr;
+        if (trace_device(q, cfg, io, depo ? n_psi : 0, s)) return -1;
         HIPCK(hipEventRecord(bs.tr[r], s));
         if (dsync()) return -1;
         if (j >= 2 && finish(j - 2)) return -1;  // before this slot's host buffer is reused

@@ -16,10 +16,11 @@
 //   torj_fan.hpp        quadrature nodes and the launch fan
 //   torj_dispatch.hpp   run-time (absorption, deposition, trajectory) -> kernel instance
 //   torj_split.hpp      the split pipeline's launches (split_trace)
-//   torj_launch.hpp     one launch of the hot path: LaunchPlan, FitLayout,
-//                       trace_device_one, trace_batched, the Gauss-Legendre upload
+//   torj_launch.hpp     one launch of the hot path: LaunchPlan, FitLayout, RayIO,
+//                       trace_device (one launch or ray batches), the Gauss-Legendre upload
 //   torj_beam.hpp       torj_trace_beam's multi-device layer
-// Here: the Gauss-Legendre table's construction and the extern "C" functions.
+// Here: the Gauss-Legendre table's construction and the extern "C" functions, which name a
+// call's arrays into a RayIO (ray entry: EntryIO) once; every host layer below takes the struct.
 // k_traj_cell is compiled in torj_traj.hip with flags of its own (-DTORJ_TRAJ_OWN_TU=1
 // here, csrc/Makefile); without that define this file is the whole library.
 #include <hip/hip_runtime.h>
@@ -64,65 +65,68 @@ static int grid_increasing(int n_psi, const double *grid) {
     return 0;
 }
 
-// A trace of n > 0 rays with n_dP rows of dP_shell: uploads, allocations, the zeroed dP,
-// `call(d, n_psi, s)` -- the device-pointer trace, its arrays in d as torj_trace_device_ex
-// takes them, n_psi 0 without deposition -- then the downloads (zeros where there was no
+// A trace of the h.n > 0 rays in the host arrays h with n_dP rows of dP_shell: uploads,
+// allocations, the zeroed dP, `call(d, n_psi, s)` -- the device-pointer trace on h's device
+// copies d, n_psi 0 without deposition -- then the downloads (zeros where there was no
 // deposition) and torj_trace_check.  Synchronous.
 template <class F>
-static int trace_staged(torj_plasma_t p, const torj_trace_cfg *cfg, int n, int n_dP, const double *x0,
-                        const double *N0, const double *weights, int n_psi, const double *grid, const double *x_launch,
-                        const double *s0, double *state, int *status, int *steps, double *dP, double *Pdep,
-                        double *traj, F call) {
-    const bool depo = n_psi >= 2 && grid;
-    const size_t rows = (size_t)n_dP * (size_t)(n_psi > 0 ? n_psi + 1 : 1);
+static int trace_staged(torj_plasma_t p, const torj_trace_cfg *cfg, const RayIO &h, int n_dP, int n_psi, F call) {
+    const int n = h.n;
+    const bool depo = n_psi >= 2 && h.psi_grid;
+    const size_t rows = dP_rows(n_dP, n_psi);
     if (ensure_device(p)) return -1;
     hipStream_t s = p->stream;
     const int n_save = cfg->traj_stride > 0 ? cfg->n_steps / cfg->traj_stride : 0;
     DevBufs B;
-    double *dx0, *dN0, *dw, *dxl, *ds0, *dgrid = nullptr, *ddP = nullptr, *dPdep = nullptr, *dstate, *dtraj;
-    int *dstatus, *dsteps;
-    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s) || B.up(&dw, weights, n, s) ||
-        B.up(&dxl, x_launch, 3 * (size_t)n, s) || B.up(&ds0, s0, n, s))
+    RayIO d{n};  // each array's device copy under its own name; no counters
+    if (B.up(&d.x0, h.x0, 3 * (size_t)n, s) || B.up(&d.N0, h.N0, 3 * (size_t)n, s) ||
+        B.up(&d.weights, h.weights, n, s) || B.up(&d.x_launch, h.x_launch, 3 * (size_t)n, s) || B.up(&d.s0, h.s0, n, s))
         return -1;
     if (depo) {
-        if (B.up(&dgrid, grid, n_psi, s) || B.alloc(&ddP, rows, true) || B.alloc(&dPdep, n, true)) return -1;
-        HIPCK(hipMemsetAsync(ddP, 0, rows * sizeof(double), s));
+        if (B.up(&d.psi_grid, h.psi_grid, n_psi, s) || B.alloc(&d.dP_shell, rows, true) || B.alloc(&d.P_dep, n, true))
+            return -1;
+        HIPCK(hipMemsetAsync(d.dP_shell, 0, rows * sizeof(double), s));
     }
-    if (B.alloc(&dstate, 7 * (size_t)n, true) || B.alloc(&dstatus, n, true) || B.alloc(&dsteps, n, true) ||
-        B.alloc(&dtraj, (size_t)n_save * 5 * n, traj && n_save > 0))
+    if (B.alloc(&d.state, 7 * (size_t)n, true) || B.alloc(&d.status, n, true) || B.alloc(&d.steps, n, true) ||
+        B.alloc(&d.traj, (size_t)n_save * 5 * n, h.traj && n_save > 0))
         return -1;
-    const torj_beam_shard d = {n, dx0, dN0, dw, dgrid, dxl, ds0, dstate, dstatus, dsteps, ddP, dPdep, dtraj, nullptr};
     if (call(d, depo ? n_psi : 0, s)) return -1;
-    if (ddownload(state, dstate, 7 * (size_t)n, s) || ddownload(status, dstatus, n, s) ||
-        ddownload(steps, dsteps, n, s))
+    if (ddownload(h.state, d.state, 7 * (size_t)n, s) || ddownload(h.status, d.status, n, s) ||
+        ddownload(h.steps, d.steps, n, s))
         return -1;
     if (depo) {
-        if (ddownload(dP, ddP, rows, s) || ddownload(Pdep, dPdep, n, s)) return -1;
+        if (ddownload(h.dP_shell, d.dP_shell, rows, s) || ddownload(h.P_dep, d.P_dep, n, s)) return -1;
     } else {
-        if (dP) std::fill(dP, dP + rows, 0.0);
-        if (Pdep) std::fill(Pdep, Pdep + n, 0.0);
+        if (h.dP_shell) std::fill(h.dP_shell, h.dP_shell + rows, 0.0);
+        if (h.P_dep) std::fill(h.P_dep, h.P_dep + n, 0.0);
     }
-    if (traj && n_save > 0 && ddownload(traj, dtraj, (size_t)n_save * 5 * n, s)) return -1;
+    if (h.traj && n_save > 0 && ddownload(h.traj, d.traj, (size_t)n_save * 5 * n, s)) return -1;
     return torj_trace_check(p, s);
 }
 
-// The ray entry of n > 0 rays: `call(dx0, dN0, dxp, dNp, ds0, dstatus, s)` is the
-// device-pointer entry.  Synchronous.
+struct EntryIO {  // the ray entry's arrays, as torj_ray_entry_device takes them
+    int n;
+    const double *x0, *N0;
+    double *xp, *Np, *s0;
+    int *status;
+};
+
+// The ray entry of the h.n > 0 rays of the host arrays h: `call(d, s)` is the device-pointer
+// entry on their device copies d.  Synchronous.
 template <class F>
-static int entry_staged(torj_plasma_t p, int n, const double *x0, const double *N0, double *xp, double *Np,
-                        double *s0, int *status, F call) {
+static int entry_staged(torj_plasma_t p, const EntryIO &h, F call) {
     if (ensure_device(p)) return -1;
     hipStream_t s = p->stream;
+    const size_t n = (size_t)h.n;
     DevBufs B;
-    double *dx0, *dN0, *dxp, *dNp, *ds0;
-    int *dst;
-    if (B.up(&dx0, x0, 3 * (size_t)n, s) || B.up(&dN0, N0, 3 * (size_t)n, s)) return -1;
-    if (B.alloc(&dxp, 3 * (size_t)n, true) || B.alloc(&dNp, 3 * (size_t)n, true) || B.alloc(&ds0, n, true) ||
-        B.alloc(&dst, n, true))
+    EntryIO d{h.n};
+    if (B.up(&d.x0, h.x0, 3 * n, s) || B.up(&d.N0, h.N0, 3 * n, s)) return -1;
+    if (B.alloc(&d.xp, 3 * n, true) || B.alloc(&d.Np, 3 * n, true) || B.alloc(&d.s0, n, true) ||
+        B.alloc(&d.status, n, true))
         return -1;
-    if (call(dx0, dN0, dxp, dNp, ds0, dst, s)) return -1;
-    if (ddownload(xp, dxp, 3 * (size_t)n, s) || ddownload(Np, dNp, 3 * (size_t)n, s) || ddownload(s0, ds0, n, s) ||
-        ddownload(status, dst, n, s))
+    if (call(d, s)) return -1;
+    if (ddownload(h.xp, d.xp, 3 * n, s) || ddownload(h.Np, d.Np, 3 * n, s) || ddownload(h.s0, d.s0, n, s) ||
+        ddownload(h.status, d.status, n, s))
         return -1;
     HIPCK(hipStreamSynchronize(s));
     return 0;
@@ -764,11 +768,11 @@ int torj_ray_entry_gpu(torj_plasma_t p, int n, const double *x0, const double *N
                        int mode, double *xp, double *Np, double *s0, int *status) {
     if (!p) return fail("bad plasma handle");
     if (n <= 0) return 0;
-    return entry_staged(p, n, x0, N0, xp, Np, s0, status,
-                        [&](const double *dx0, const double *dN0, double *dxp, double *dNp, double *ds0, int *dst,
-                            hipStream_t s) {
-                            return torj_ray_entry_device(p, n, dx0, dN0, omega, mode, dxp, dNp, ds0, dst, s);
-                        });
+    EntryIO io{};
+    io.n = n, io.x0 = x0, io.N0 = N0, io.xp = xp, io.Np = Np, io.s0 = s0, io.status = status;
+    return entry_staged(p, io, [&](const EntryIO &d, hipStream_t s) {
+        return torj_ray_entry_device(p, d.n, d.x0, d.N0, omega, mode, d.xp, d.Np, d.s0, d.status, s);
+    });
 }
 
 int torj_trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
@@ -784,102 +788,57 @@ int torj_trace_device_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, cons
                          const double *x_launch, const double *s0, double *state, int *status,
                          int *steps, double *dP, double *Pdep, double *traj, uint64_t *counters,
                          void *stream) {
-    if (!p || !cfg) return fail("bad plasma handle or cfg");
-    if (n <= 0) return 0;
-    return on_caller_stream(p, stream, [&](hipStream_t s) {
-        if (p->timing) p->timing_calls++;
-        const bool fit = n_psi >= 2 && grid && dP && cfg->deposition == 1;
-        // TORJ_SPLIT_BATCH=R (read per call; fixed-step absorbing beams): trace in
-        // contiguous batches of R rays (a multiple of 64), each its own pipeline
-        const long sb_rays =
-            (cfg->integrator == 0 && cfg->absorption >= 1) ? env_long("TORJ_SPLIT_BATCH", 0) / 64 * 64 : 0;
-        if ((fit || sb_rays > 0) && cfg->n_steps > 0 && x0 && N0 && state && status && steps) {
-            const size_t per_ray =
-                fit ? fit_bytes_per_ray((size_t)cfg->n_steps + 2, (size_t)n_psi, cfg->integrator == 1) : 0;
-            if (ensure_device(p)) return -1;
-            const size_t nb = batch_rays((size_t)n, per_ray, ws_budget(p), sb_rays);
-            if (nb < (size_t)n)
-                return trace_batched(p, cfg, n, (int)nb, x0, N0, weights, n_psi, grid, x_launch, s0, state, status,
-                                     steps, dP, Pdep, traj, counters, s);
-        }
-        return trace_device_one(p, cfg, n, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps, dP, Pdep,
-                                traj, counters, s);
-    });
+    RayIO io{};
+    io.n = n, io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.dP_shell = dP, io.P_dep = Pdep, io.traj = traj;
+    io.counters = counters;
+    return trace_device(p, cfg, io, n_psi, stream);
 }
 
 // ---- many beams of differing frequency and mode in one launch (beams_plan, torj_k_beams.hpp),
 // and through differing plasmas (`ps`: beams_plasmas_plan) ----
 }  // extern "C"
 
-static int beams_device_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
-                              const int *beam_off, const double *omega, const int *mode, const double *x0,
-                              const double *N0, const double *weights, int n_psi, const double *grid,
-                              const double *x_launch, const double *s0, double *state, int *status, int *steps,
-                              double *dP, double *Pdep, double *traj, uint64_t *counters, void *stream) {
+// host pointers, synchronous, checked
+static int beams_host_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, const BeamTables &bt,
+                            const RayIO &caller, int n_psi) {
     if (!p || !cfg) return fail("bad plasma handle or cfg");
-    if (!stream) {  // on_caller_stream's fork needs the device: argument errors first, without one
-        BeamsPlasmasPlan pp;
-        const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
-                                x_launch != nullptr, s0 != nullptr, traj != nullptr};
-        if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
+    const bool depo = n_psi >= 2 && caller.psi_grid;
+    BeamsPlasmasPlan pp;  // argument errors before any device work (the device form repeats them on its pointers)
+    LaunchPtrs has = launch_ptrs(caller);
+    has.grid = has.dP = depo;  // host arrays: the device form gets both from trace_staged exactly when depo
+    if (beams_any_plan(pp, p, ps, *cfg, bt, n_psi, has) || (depo && grid_increasing(n_psi, caller.psi_grid))) return -1;
+    RayIO h = caller;
+    h.n = bt.beam_off[bt.n_beams];
+    if (h.n == 0) {
+        if (h.dP_shell) std::fill(h.dP_shell, h.dP_shell + dP_rows(bt.n_beams, n_psi), 0.0);
+        return 0;
     }
-    return on_caller_stream(p, stream, [&](hipStream_t s) {
-        if (p->timing) p->timing_calls++;
-        return beams_trace_device(p, ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch,
-                                  s0, state, status, steps, dP, Pdep, traj, counters, s);
+    return trace_staged(p, cfg, h, bt.n_beams, n_psi, [&](const RayIO &d, int n_psi_d, hipStream_t s) {
+        return beams_trace_device(p, ps, cfg, bt, d, n_psi_d, s);
     });
 }
 
-// host pointers, synchronous, checked
-static int beams_host_entry(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
-                            const int *beam_off, const double *omega, const int *mode, const double *x0,
-                            const double *N0, const double *weights, int n_psi, const double *grid,
-                            const double *x_launch, const double *s0, double *state, int *status, int *steps,
-                            double *dP, double *Pdep, double *traj) {
-    if (!p || !cfg) return fail("bad plasma handle or cfg");
-    const bool depo = n_psi >= 2 && grid;
-    {  // argument errors before any device work (the device form repeats them on its pointers)
-        BeamsPlasmasPlan pp;
-        const LaunchPtrs has = {x0 && N0 && state && status && steps, depo, depo, x_launch != nullptr,
-                                s0 != nullptr, traj != nullptr};
-        if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
-    }
-    if (depo && grid_increasing(n_psi, grid)) return -1;
-    const int n = beam_off[n_beams];
-    if (n == 0) {
-        if (dP) std::fill(dP, dP + (size_t)n_beams * (size_t)(n_psi > 0 ? n_psi + 1 : 1), 0.0);
-        return 0;
-    }
-    return trace_staged(p, cfg, n, n_beams, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps, dP, Pdep,
-                        traj, [&](const torj_beam_shard &d, int n_psi_d, hipStream_t s) {
-                            return beams_device_entry(p, ps, cfg, n_beams, beam_off, omega, mode, d.x0, d.N0,
-                                                      d.weights, n_psi_d, d.psi_grid, d.x_launch, d.s0, d.state,
-                                                      d.status, d.steps, d.dP_shell, d.P_dep, d.traj, nullptr, s);
-                        });
-}
-
 // the ray entry's argument errors: the tables', then the arrays'; no HIP call
-static int entry_beams_check(torj_plasma_t p, const PlasmaSel *ps, int n_beams, const int *beam_off,
-                             const double *omega, const int *mode, const double *x0, const double *N0, double *xp,
-                             double *Np, double *s0, int *status) {
+static int entry_beams_check(torj_plasma_t p, const PlasmaSel *ps, const BeamTables &bt, const EntryIO &io) {
     if (!p) return fail("bad plasma handle");
     if (ps && beams_plasmas_check(ps->n, (const void *const *)ps->list, ps->beam_plasma, p->device, kHandleView))
         return -1;
-    if (beams_tables_check(n_beams, beam_off, omega, mode)) return -1;
-    if (ps && beam_plasma_check(ps->n, ps->beam_plasma, n_beams)) return -1;
-    if (!x0 || !N0 || !xp || !Np || !s0 || !status) return fail("x0, N0, x_plasma, N_plasma, s0, status required");
+    if (beams_tables_check(bt.n_beams, bt.beam_off, bt.omega, bt.mode)) return -1;
+    if (ps && beam_plasma_check(ps->n, ps->beam_plasma, bt.n_beams)) return -1;
+    if (!io.x0 || !io.N0 || !io.xp || !io.Np || !io.s0 || !io.status)
+        return fail("x0, N0, x_plasma, N_plasma, s0, status required");
     return 0;
 }
 
-static int entry_beams_device(torj_plasma_t p, const PlasmaSel *ps, int n_beams, const int *beam_off,
-                              const double *omega, const int *mode, const double *x0, const double *N0, double *xp,
-                              double *Np, double *s0, int *status, void *stream) {
-    if (entry_beams_check(p, ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status)) return -1;
-    const int n = beam_off[n_beams];
+static int entry_beams_device(torj_plasma_t p, const PlasmaSel *ps, const BeamTables &bt, const EntryIO &io,
+                              void *stream) {
+    if (entry_beams_check(p, ps, bt, io)) return -1;
+    const int n_beams = bt.n_beams, n = bt.beam_off[n_beams];
     if (n == 0) return 0;
     if (ensure_devices(p, ps)) return -1;
     const dim3 grd(nblocks(n, 64)), blk(64);
-    EntryArgs a{p->d_coef, p->g, p->psi_prof_max, 0.0, 0, n, x0, N0, xp, Np, s0, status};
+    EntryArgs a{p->d_coef, p->g, p->psi_prof_max, 0.0, 0, n, io.x0, io.N0, io.xp, io.Np, io.s0, io.status};
     std::vector<PlasmaRec> plasmas;
     std::vector<int> beam_pl;
     if (ps) {
@@ -889,8 +848,8 @@ static int entry_beams_device(torj_plasma_t p, const PlasmaSel *ps, int n_beams,
     const BeamRec *d_beams;
     const PlasmaRec *d_plasmas;
     const int *d_beam_pl;
-    if (beams_upload(p, beams_records(n_beams, beam_off, omega, mode), {}, plasmas, beam_pl, (hipStream_t)stream,
-                     &d_beams, nullptr, &d_plasmas, &d_beam_pl))
+    if (beams_upload(p, beams_records(n_beams, bt.beam_off, bt.omega, bt.mode), {}, plasmas, beam_pl,
+                     (hipStream_t)stream, &d_beams, nullptr, &d_plasmas, &d_beam_pl))
         return -1;
     if (ps)
         hipLaunchKernelGGL(k_ray_entry_beams, grd, blk, 0, (hipStream_t)stream, a, d_beams, n_beams, d_plasmas,
@@ -901,18 +860,12 @@ static int entry_beams_device(torj_plasma_t p, const PlasmaSel *ps, int n_beams,
     return 0;
 }
 
-static int entry_beams_host(torj_plasma_t p, const PlasmaSel *ps, int n_beams, const int *beam_off,
-                            const double *omega, const int *mode, const double *x0, const double *N0, double *xp,
-                            double *Np, double *s0, int *status) {
-    if (entry_beams_check(p, ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status)) return -1;
-    const int n = beam_off[n_beams];
-    if (n == 0) return 0;
-    return entry_staged(p, n, x0, N0, xp, Np, s0, status,
-                        [&](const double *dx0, const double *dN0, double *dxp, double *dNp, double *ds0, int *dst,
-                            hipStream_t s) {
-                            return entry_beams_device(p, ps, n_beams, beam_off, omega, mode, dx0, dN0, dxp, dNp, ds0,
-                                                      dst, s);
-                        });
+static int entry_beams_host(torj_plasma_t p, const PlasmaSel *ps, const BeamTables &bt, const EntryIO &caller) {
+    if (entry_beams_check(p, ps, bt, caller)) return -1;
+    EntryIO h = caller;
+    h.n = bt.beam_off[bt.n_beams];
+    if (h.n == 0) return 0;
+    return entry_staged(p, h, [&](const EntryIO &d, hipStream_t s) { return entry_beams_device(p, ps, bt, d, s); });
 }
 
 extern "C" {
@@ -922,8 +875,12 @@ int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_be
                             const double *weights, int n_psi, const double *grid, const double *x_launch,
                             const double *s0, double *state, int *status, int *steps, double *dP,
                             double *Pdep, double *traj, uint64_t *counters, void *stream) {
-    return beams_device_entry(p, nullptr, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch,
-                              s0, state, status, steps, dP, Pdep, traj, counters, stream);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    RayIO io{};
+    io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.dP_shell = dP, io.P_dep = Pdep, io.traj = traj;
+    io.counters = counters;
+    return beams_trace_device(p, nullptr, cfg, bt, io, n_psi, stream);
 }
 
 int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
@@ -931,20 +888,29 @@ int torj_trace_beams(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, co
                      const double *weights, int n_psi, const double *grid, const double *x_launch,
                      const double *s0, double *state, int *status, int *steps, double *dP, double *Pdep,
                      double *traj) {
-    return beams_host_entry(p, nullptr, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch,
-                            s0, state, status, steps, dP, Pdep, traj);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    RayIO io{};
+    io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.dP_shell = dP, io.P_dep = Pdep, io.traj = traj;
+    return beams_host_entry(p, nullptr, cfg, bt, io, n_psi);
 }
 
 int torj_ray_entry_beams_device(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
                                 const int *mode, const double *x0, const double *N0, double *xp, double *Np,
                                 double *s0, int *status, void *stream) {
-    return entry_beams_device(p, nullptr, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status, stream);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    EntryIO io{};
+    io.x0 = x0, io.N0 = N0, io.xp = xp, io.Np = Np, io.s0 = s0, io.status = status;
+    return entry_beams_device(p, nullptr, bt, io, stream);
 }
 
 int torj_ray_entry_beams_gpu(torj_plasma_t p, int n_beams, const int *beam_off, const double *omega,
                              const int *mode, const double *x0, const double *N0, double *xp, double *Np,
                              double *s0, int *status) {
-    return entry_beams_host(p, nullptr, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    EntryIO io{};
+    io.x0 = x0, io.N0 = N0, io.xp = xp, io.Np = Np, io.s0 = s0, io.status = status;
+    return entry_beams_host(p, nullptr, bt, io);
 }
 
 // beam b through plasmas[beam_plasma[b]]; p is the launch's handle (stream, scratch, flags, knobs)
@@ -956,8 +922,12 @@ int torj_trace_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const torj_p
                                     int *steps, double *dP, double *Pdep, double *traj, uint64_t *counters,
                                     void *stream) {
     const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
-    return beams_device_entry(p, &ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
-                              state, status, steps, dP, Pdep, traj, counters, stream);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    RayIO io{};
+    io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.dP_shell = dP, io.P_dep = Pdep, io.traj = traj;
+    io.counters = counters;
+    return beams_trace_device(p, &ps, cfg, bt, io, n_psi, stream);
 }
 
 int torj_trace_beams_plasmas(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas, const int *beam_plasma,
@@ -966,8 +936,11 @@ int torj_trace_beams_plasmas(torj_plasma_t p, int n_plasmas, const torj_plasma_t
                              const double *grid, const double *x_launch, const double *s0, double *state,
                              int *status, int *steps, double *dP, double *Pdep, double *traj) {
     const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
-    return beams_host_entry(p, &ps, cfg, n_beams, beam_off, omega, mode, x0, N0, weights, n_psi, grid, x_launch, s0,
-                            state, status, steps, dP, Pdep, traj);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    RayIO io{};
+    io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.dP_shell = dP, io.P_dep = Pdep, io.traj = traj;
+    return beams_host_entry(p, &ps, cfg, bt, io, n_psi);
 }
 
 int torj_ray_entry_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
@@ -975,7 +948,10 @@ int torj_ray_entry_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const to
                                         const double *omega, const int *mode, const double *x0, const double *N0,
                                         double *xp, double *Np, double *s0, int *status, void *stream) {
     const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
-    return entry_beams_device(p, &ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status, stream);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    EntryIO io{};
+    io.x0 = x0, io.N0 = N0, io.xp = xp, io.Np = Np, io.s0 = s0, io.status = status;
+    return entry_beams_device(p, &ps, bt, io, stream);
 }
 
 int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
@@ -983,7 +959,10 @@ int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_
                                      const int *mode, const double *x0, const double *N0, double *xp, double *Np,
                                      double *s0, int *status) {
     const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
-    return entry_beams_host(p, &ps, n_beams, beam_off, omega, mode, x0, N0, xp, Np, s0, status);
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    EntryIO io{};
+    io.x0 = x0, io.N0 = N0, io.xp = xp, io.Np = Np, io.s0 = s0, io.status = status;
+    return entry_beams_host(p, &ps, bt, io);
 }
 
 int torj_power_deposition_profile(torj_plasma_t p, int n_rays, const int *n_points, const double *s,
@@ -1165,12 +1144,12 @@ int torj_trace_ex(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const doubl
     if (n <= 0) return 0;
     // (the grid's host copy is at hand: checked before any device work)
     if (n_psi >= 2 && grid && grid_increasing(n_psi, grid)) return -1;
-    return trace_staged(p, cfg, n, 1, x0, N0, weights, n_psi, grid, x_launch, s0, state, status, steps, dP, Pdep, traj,
-                        [&](const torj_beam_shard &d, int n_psi_d, hipStream_t s) {
-                            return torj_trace_device_ex(p, cfg, n, d.x0, d.N0, d.weights, n_psi_d, d.psi_grid,
-                                                        d.x_launch, d.s0, d.state, d.status, d.steps, d.dP_shell,
-                                                        d.P_dep, d.traj, nullptr, s);
-                        });
+    RayIO io{};
+    io.n = n, io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.dP_shell = dP, io.P_dep = Pdep, io.traj = traj;
+    return trace_staged(p, cfg, io, 1, n_psi, [&](const RayIO &d, int n_psi_d, hipStream_t s) {
+        return trace_device(p, cfg, d, n_psi_d, s);
+    });
 }
 
 int torj_trace_beam(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
@@ -1195,11 +1174,13 @@ int torj_trace_beam(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const dou
     const bool reduce = depo && (n_gpus > 1 || env_int("TORJ_BEAM_RCCL", 0) != 0);  // read per call (tests toggle it)
     // per-device partial dP_shell, then one all-reduce
     std::vector<double *> d_dP(n_gpus, nullptr);
+    RayIO io{};  // the whole beam's host arrays (dP_shell: downloaded here, after the reduce)
+    io.n = n, io.x0 = x0, io.N0 = N0, io.weights = weights, io.psi_grid = grid, io.x_launch = x_launch, io.s0 = s0;
+    io.state = state, io.status = status, io.steps = steps, io.P_dep = Pdep, io.traj = traj;
     int out = beam_fanout(p, n_gpus, "torj_trace_beam", [&](int k) -> int {
         torj_plasma_s *q = p->replicas[k];
         if (depo) HIPCK(hipMalloc(&d_dP[k], (n_psi + 1) * sizeof(double)));
-        return beam_worker(q, cfg, n, S, k, n_gpus, x0, N0, weights, n_psi, grid, x_launch, s0, state,
-                           status, steps, depo ? Pdep : nullptr, traj, d_dP[k]);
+        return beam_worker(q, cfg, io, S, k, n_gpus, n_psi, d_dP[k]);
     });
     if (!out && reduce) out = beam_reduce(p, n_gpus, d_dP, n_psi, same);
     if (!out && depo) {
@@ -1217,7 +1198,7 @@ int torj_trace_beam(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const dou
             (void)hipFree(d_dP[k]);
         }
     if (!out && !depo) {
-        if (dP) std::fill(dP, dP + (n_psi > 0 ? n_psi + 1 : 1), 0.0);
+        if (dP) std::fill(dP, dP + dP_rows(1, n_psi), 0.0);
         if (Pdep) std::fill(Pdep, Pdep + n, 0.0);
     }
     (void)hipSetDevice(p->device);
@@ -1238,13 +1219,7 @@ int torj_trace_beam_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_gpu
     const bool reduce = depo && (n_gpus > 1 || env_int("TORJ_BEAM_RCCL", 0) != 0);
     int out = beam_fanout(p, n_gpus, "torj_trace_beam_device", [&](int k) -> int {
         torj_plasma_s *q = p->replicas[k];
-        const torj_beam_shard &h = shards[k];
-        if (ensure_device(q)) return -1;
-        if (h.n > 0 &&
-            torj_trace_device_ex(q, cfg, h.n, h.x0, h.N0, h.weights, depo ? n_psi : 0, h.psi_grid,
-                                 h.x_launch, h.s0, h.state, h.status, h.steps, h.dP_shell, h.P_dep,
-                                 h.traj, h.counters, q->stream))
-            return -1;
+        if (ensure_device(q) || trace_device(q, cfg, shards[k], depo ? n_psi : 0, q->stream)) return -1;
         return torj_trace_check(q, q->stream);  // waits for the stream: queue / grid flags
     });
     if (!out && reduce) {

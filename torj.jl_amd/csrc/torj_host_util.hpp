@@ -110,6 +110,10 @@ struct DevBufs {
         track(*d);
         return r;
     }
+    template <typename T>  // ... into a field that is an input where it is used (RayIO's, EntryIO's)
+    int up(const T **d, const T *h, size_t n, hipStream_t s) {
+        return up(const_cast<T **>(d), h, n, s);
+    }
     template <typename T>
     int alloc(T **d, size_t n, bool want) {
         const int r = dalloc(d, n, want);

@@ -5,12 +5,12 @@
 // thresholds on the CPU); fit_layout is the reference deposition's workspace,
 // written once for the trace, torj_power_deposition_profile and the batch size;
 // trace_device_one enqueues what the plan says, one short launcher per path;
-// trace_batched is torj_trace_device_ex's loop over ray batches; beams_plan and
+// trace_batched is trace_device's loop over ray batches; beams_plan and
 // beams_trace_device are the same two steps for a multi-beam launch, and
 // beams_plasmas_plan adds a plasma per beam to that plan.  trace_prologue is what
 // both enqueue ahead of their trace kernels, on_caller_stream the NULL stream's
-// fork and join around either.  Also here, ahead of its first user: the
-// Gauss-Legendre table's upload.
+// fork and join around either; a call's arrays reach all of them as one RayIO.
+// Also here, ahead of its first user: the Gauss-Legendre table's upload.
 // The planning comes first and needs no kernel header: TORJ_LAUNCH_PLAN_ONLY
 // stops there (the CPU test's harness).
 // (a slice of torj_hip.hip: included after `using namespace torj`)
@@ -455,17 +455,27 @@ static int on_caller_stream(torj_plasma_s *p, void *stream, F call) {
     return rc;
 }
 
+// ---- RayIO: a trace's ray count and arrays, passed on by every host layer below the extern "C"
+// functions (a layer's own arrays: set by name on a copy); n_psi beside it, 0 without deposition ----
+using RayIO = torj_beam_shard;
+static LaunchPtrs launch_ptrs(const RayIO &io) {  // which of its pointers are given
+    return {io.x0 && io.N0 && io.state && io.status && io.steps, io.psi_grid != nullptr, io.dP_shell != nullptr,
+            io.x_launch != nullptr, io.s0 != nullptr, io.traj != nullptr};
+}
+// doubles in n_dP rows of dP_shell: n_psi + 1 each (one where there is no grid)
+static size_t dP_rows(int n_dP, int n_psi) { return (size_t)n_dP * (size_t)(n_psi > 0 ? n_psi + 1 : 1); }
+// the host tables of a multi-beam call, in the order every entry takes them
+struct BeamTables { int n_beams; const int *beam_off; const double *omega; const int *mode; };
+
 // the kernels' arguments that come from the handle, the cfg and the caller's arrays alone
-static TraceArgs trace_args(const torj_plasma_s *p, const torj_trace_cfg &cfg, int n, const double *x0,
-                            const double *N0, const double *weights, const double *s0, double *state,
-                            int *status, int *steps, uint64_t *counters) {
+static TraceArgs trace_args(const torj_plasma_s *p, const torj_trace_cfg &cfg, const RayIO &io) {
     TraceArgs a{};
     a.coef = p->d_coef, a.cellp = p->d_cellp, a.g = p->g;
     a.k = make_consts(cfg.omega), a.omega = cfg.omega, a.mode = cfg.mode, a.abs_model = cfg.absorption;
     a.ds = cfg.ds, a.n_steps = cfg.n_steps, a.chunk_steps = cfg.chunk_steps;
     a.psi_exit = cfg.psi_exit, a.P_min = cfg.P_min;
-    a.n = n, a.x0 = x0, a.N0 = N0, a.w = weights, a.s0 = s0;
-    a.state = state, a.status = status, a.steps = steps, a.counters = (unsigned long long *)counters;
+    a.n = io.n, a.x0 = io.x0, a.N0 = io.N0, a.w = io.weights, a.s0 = io.s0;
+    a.state = io.state, a.status = io.status, a.steps = io.steps, a.counters = (unsigned long long *)io.counters;
     if (cfg.integrator == 1) {
         a.abstol = cfg.abstol, a.reltol = cfg.reltol;
         a.s_step = cfg.s_max / cfg.n_chunks, a.n_chunks = cfg.n_chunks;
@@ -489,52 +499,45 @@ static void fit_args(FitArgs &fa, const TraceArgs &a, const double *x_launch, bo
 // k_grid_check, the NaN fill of traj, fit_zero and the timing's first event.
 // zero = false leaves fit_zero to the caller.
 template <class Plan>
-static int trace_prologue(torj_plasma_s *p, const Plan &pl, const torj_trace_cfg &cfg, int n_psi, const double *grid,
-                          const double *x_launch, double *dP, double *Pdep, double *traj, bool s_uniform, bool zero,
-                          TraceArgs &a, FitArgs &fa, hipEvent_t ev[3], hipStream_t s) {
+static int trace_prologue(torj_plasma_s *p, const Plan &pl, const torj_trace_cfg &cfg, const RayIO &io, int n_psi,
+                          bool s_uniform, bool zero, TraceArgs &a, FitArgs &fa, hipEvent_t ev[3], hipStream_t s) {
     if (pl.depo) {
         a.n_psi = n_psi;
-        a.grid = grid;  // uniform-grid fast path is set up in-kernel from grid[0], grid[n-1]
-        a.dP = dP;
-        if (!Pdep) {  // the work-queue kernel carries P_dep across chunks: workspace
+        a.grid = io.psi_grid;  // uniform-grid fast path is set up in-kernel from grid[0], grid[n-1]
+        a.dP = io.dP_shell, a.Pdep = io.P_dep;
+        if (!a.Pdep) {  // the work-queue kernel carries P_dep across chunks: workspace
             if (ensure_buf(p, p->ws, (size_t)a.n * sizeof(double))) return -1;
-            Pdep = (double *)p->ws.d;
+            a.Pdep = (double *)p->ws.d;
         }
-        a.Pdep = Pdep;
     }
     if (pl.fit) {
         if (ensure_buf(p, p->fit, pl.lay.bytes())) return -1;
         fit_point(pl.lay, (char *)p->fit.d, fa, &a);
-        fit_args(fa, a, x_launch, s_uniform);
+        fit_args(fa, a, io.x_launch, s_uniform);
     }
     if (pl.depo)  // psi_dP_dV strictly increasing: checked on the device, reported by torj_trace_check
-        hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, grid, n_psi, p->d_flags);
+        hipLaunchKernelGGL(k_grid_check, dim3(1), dim3(256), 0, s, io.psi_grid, n_psi, p->d_flags);
     if (pl.tr) {
-        a.traj_stride = cfg.traj_stride, a.n_save = pl.n_save, a.traj = traj;
+        a.traj_stride = cfg.traj_stride, a.n_save = pl.n_save, a.traj = io.traj;
         if (a.n_save > 0)
-            HIPCK(hipMemsetAsync(traj, 0xFF, (size_t)a.n_save * 5 * a.n * sizeof(double), s));  // NaN
+            HIPCK(hipMemsetAsync(io.traj, 0xFF, (size_t)a.n_save * 5 * a.n * sizeof(double), s));  // NaN
     }
     if (pl.fit && zero && fit_zero(fa, s)) return -1;
     return timing_begin(p, ev, s);
 }
 
-// one launch of the hot path over n rays (the body of torj_trace_device_ex)
-static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, const double *x0,
-                            const double *N0, const double *weights, int n_psi, const double *grid,
-                            const double *x_launch, const double *s0, double *state, int *status,
-                            int *steps, double *dP, double *Pdep, double *traj, uint64_t *counters,
-                            void *stream) {
+// one launch of the hot path over io.n rays
+static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, const RayIO &io, int n_psi, hipStream_t s) {
+    const int n = io.n;
     if (n <= 0) return 0;
-    const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
-                            x_launch != nullptr, s0 != nullptr, traj != nullptr};
+    const LaunchPtrs has = launch_ptrs(io);
     LaunchPlan pl;
     const bool fresh = !p->d_flags;  // n_cu is the device's only once ensure_device has run
     if (launch_plan(pl, *cfg, n, n_psi, has, launch_knobs(p))) return -1;  // argument errors need no device
     if (ensure_device(p)) return -1;
     if (fresh && launch_plan(pl, *cfg, n, n_psi, has, launch_knobs(p))) return -1;
     if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    TraceArgs a = trace_args(p, *cfg, n, x0, N0, weights, s0, state, status, steps, counters);
+    TraceArgs a = trace_args(p, *cfg, io);
     if (pl.adaptive) {
         if (ensure_buf(p, p->chunk, (size_t)n * sizeof(int))) return -1;
         a.chunk = (int *)p->chunk.d;
@@ -544,9 +547,7 @@ static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, int n, c
     // clears it on its scan stream, overlapped with the first trajectory block
     FitArgs fa{};
     hipEvent_t ev[3];
-    if (trace_prologue(p, pl, *cfg, n_psi, grid, x_launch, dP, Pdep, traj, !pl.adaptive, pl.path != kPathSplit, a, fa,
-                       ev, s))
-        return -1;
+    if (trace_prologue(p, pl, *cfg, io, n_psi, !pl.adaptive, pl.path != kPathSplit, a, fa, ev, s)) return -1;
     DepoStream dstr{};  // the split pipeline's streamed deposition (split_trace)
     switch (pl.path) {
     case kPathSplit:
@@ -615,11 +616,10 @@ static const PlasmaView kHandleView = {
 
 // beams_plan, or beams_plasmas_plan when plasmas are given: argument errors, no HIP call
 static int beams_any_plan(BeamsPlasmasPlan &pp, const torj_plasma_s *p, const PlasmaSel *ps, const torj_trace_cfg &cfg,
-                          int n_beams, const int *beam_off, const double *omega, const int *mode, int n_psi,
-                          const LaunchPtrs &has) {
-    if (!ps) return beams_plan(pp.bp, cfg, n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p));
+                          const BeamTables &bt, int n_psi, const LaunchPtrs &has) {
+    if (!ps) return beams_plan(pp.bp, cfg, bt.n_beams, bt.beam_off, bt.omega, bt.mode, n_psi, has, launch_knobs(p));
     return beams_plasmas_plan(pp, cfg, ps->n, (const void *const *)ps->list, ps->beam_plasma, p->device, kHandleView,
-                              n_beams, beam_off, omega, mode, n_psi, has, launch_knobs(p));
+                              bt.n_beams, bt.beam_off, bt.omega, bt.mode, n_psi, has, launch_knobs(p));
 }
 
 // the device state of every listed handle, then the launching one's (created on a
@@ -667,64 +667,64 @@ static int launch_post_beams(const BA &ba, const FitArgs &fa, hipStream_t s) {
     return 0;
 }
 
-// one multi-beam launch on stream `s` (the body of torj_trace_beams_device and, with
-// `ps`, of torj_trace_beams_plasmas_device); the host tables are consumed before it returns
-static int beams_trace_device(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, int n_beams,
-                              const int *beam_off,
-                              const double *omega, const int *mode, const double *x0, const double *N0,
-                              const double *weights, int n_psi, const double *grid, const double *x_launch,
-                              const double *s0, double *state, int *status, int *steps, double *dP,
-                              double *Pdep, double *traj, uint64_t *counters, hipStream_t s) {
-    const LaunchPtrs has = {x0 && N0 && state && status && steps, grid != nullptr, dP != nullptr,
-                            x_launch != nullptr, s0 != nullptr, traj != nullptr};
+// one multi-beam launch on the caller's stream (the body of torj_trace_beams_device and, with `ps`, of
+// torj_trace_beams_plasmas_device); the host tables are consumed before it returns
+static int beams_trace_device(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, const BeamTables &bt,
+                              const RayIO &caller, int n_psi, void *stream) {
+    if (!p || !cfg) return fail("bad plasma handle or cfg");
+    const LaunchPtrs has = launch_ptrs(caller);
     BeamsPlasmasPlan pp;
     const BeamsPlan &bp = pp.bp;
     const bool fresh = !p->d_flags;  // n_cu is the device's only once ensure_device has run
-    if (beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
-    if (ensure_devices(p, ps)) return -1;
-    // (again with plasmas: their records hold device pointers, which exist only now)
-    if ((fresh || ps) && beams_any_plan(pp, p, ps, *cfg, n_beams, beam_off, omega, mode, n_psi, has)) return -1;
-    const int n = bp.n;
-    if (n == 0) return 0;
-    if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
-    if (bp.fit) {
-        const size_t budget = ws_budget(p);
-        if (bp.lay.bytes() > budget)
-            return fail("multi-beam launch: the reference deposition's workspace for %d rays (%zu bytes) exceeds "
-                        "the budget of %zu bytes (TORJ_WS_GB); trace the beams in separate calls",
-                        n, bp.lay.bytes(), budget);
-    }
-    BeamsPlArgs pa{};
-    BeamsArgs &ba = pa;
-    torj_trace_cfg c1 = *cfg;  // (omega and mode are the beams'; any valid pair here)
-    c1.omega = omega[0], c1.mode = mode[0];
-    // (with plasmas a.coef, a.cellp and a.g are p's and unused: the beam's plasma record gives them)
-    TraceArgs &a = ba.a = trace_args(p, c1, n, x0, N0, weights, s0, state, status, steps, counters);
-    ba.n_beams = n_beams;
-    if (beams_upload(p, bp.beams, bp.waves, pp.plasmas, pp.beam_pl, s, &ba.beams, &ba.waves, &pa.plasmas, &pa.beam_pl))
-        return -1;
-    FitArgs fa{};
-    hipEvent_t ev[3];
-    if (trace_prologue(p, bp, *cfg, n_psi, grid, x_launch, dP, Pdep, traj, true, true, a, fa, ev, s)) return -1;
-    auto run = [&](const auto &args) -> int {  // the trace and the phase after it, on either argument struct
-        launch_beams(args, bp, s);
-        HIPCK(hipGetLastError());
-        if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
-        if (bp.fit && launch_post_beams(args, fa, s)) return -1;
-        if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
-        return 0;
-    };
-    return ps ? run(pa) : run(ba);
+    // argument errors need no device: before the NULL stream's fork touches one
+    if (beams_any_plan(pp, p, ps, *cfg, bt, n_psi, has)) return -1;
+    return on_caller_stream(p, stream, [&](hipStream_t s) -> int {
+        if (p->timing) p->timing_calls++;
+        if (ensure_devices(p, ps)) return -1;
+        // (again with plasmas: their records hold device pointers, which exist only now)
+        if ((fresh || ps) && beams_any_plan(pp, p, ps, *cfg, bt, n_psi, has)) return -1;
+        RayIO io = caller;
+        const int n = io.n = bp.n;  // the plan's: beam_off[n_beams]
+        if (n == 0) return 0;
+        if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
+        if (bp.fit) {
+            const size_t budget = ws_budget(p);
+            if (bp.lay.bytes() > budget)
+                return fail("multi-beam launch: the reference deposition's workspace for %d rays (%zu bytes) exceeds "
+                            "the budget of %zu bytes (TORJ_WS_GB); trace the beams in separate calls",
+                            n, bp.lay.bytes(), budget);
+        }
+        BeamsPlArgs pa{};
+        BeamsArgs &ba = pa;
+        torj_trace_cfg c1 = *cfg;  // (omega and mode are the beams'; any valid pair here)
+        c1.omega = bt.omega[0], c1.mode = bt.mode[0];
+        // (with plasmas a.coef, a.cellp and a.g are p's and unused: the beam's plasma record gives them)
+        TraceArgs &a = ba.a = trace_args(p, c1, io);
+        ba.n_beams = bt.n_beams;
+        if (beams_upload(p, bp.beams, bp.waves, pp.plasmas, pp.beam_pl, s, &ba.beams, &ba.waves, &pa.plasmas,
+                         &pa.beam_pl))
+            return -1;
+        FitArgs fa{};
+        hipEvent_t ev[3];
+        if (trace_prologue(p, bp, *cfg, io, n_psi, true, true, a, fa, ev, s)) return -1;
+        auto run = [&](const auto &args) -> int {  // the trace and the phase after it, on either argument struct
+            launch_beams(args, bp, s);
+            HIPCK(hipGetLastError());
+            if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
+            if (bp.fit && launch_post_beams(args, fa, s)) return -1;
+            if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
+            return 0;
+        };
+        return ps ? run(pa) : run(ba);
+    });
 }
 
-// ---- ray batches (torj_trace_device_ex): the beam in contiguous batches of nb
+// ---- ray batches (trace_device): the beam in contiguous batches of nb
 // rays, each its own trace_device_one; the batch's inputs gathered into and its
 // outputs scattered from compact staging ----
-static int trace_batched(torj_plasma_t p, const torj_trace_cfg *cfg, int n, int nb, const double *x0,
-                         const double *N0, const double *weights, int n_psi, const double *grid,
-                         const double *x_launch, const double *s0, double *state, int *status, int *steps,
-                         double *dP, double *Pdep, double *traj, uint64_t *counters, hipStream_t s) {
-    const int n_save = cfg->traj_stride > 0 && traj ? cfg->n_steps / cfg->traj_stride : 0;
+static int trace_batched(torj_plasma_t p, const torj_trace_cfg *cfg, const RayIO &io, int nb, int n_psi,
+                         hipStream_t s) {
+    const int n = io.n, n_save = cfg->traj_stride > 0 && io.traj ? cfg->n_steps / cfg->traj_stride : 0;
     const size_t D = sizeof(double), B = (size_t)nb;
     // the staging's double arrays and their rows per ray, in the buffer's order;
     // status and steps (int) follow them
@@ -734,9 +734,13 @@ static int trace_batched(torj_plasma_t p, const torj_trace_cfg *cfg, int n, int 
     for (int k = 0; k < kNb; k++) off[k + 1] = off[k] + (size_t)rows[k];
     if (ensure_buf(p, p->batch, off[kNb] * B * D + 2 * B * sizeof(int))) return -1;
     auto b = [&](int k) { return (double *)p->batch.d + off[k] * B; };
-    int *bstat = (int *)b(kNb), *bsteps = bstat + B;
+    RayIO bio = io;  // a batch's: staging rows; psi_grid, dP_shell and counters the caller's, shared by all
+    bio.x0 = b(kX0), bio.N0 = b(kN0), bio.state = b(kSt), bio.P_dep = b(kP);
+    bio.status = (int *)b(kNb), bio.steps = bio.status + B;
+    bio.weights = io.weights ? b(kW) : nullptr, bio.x_launch = io.x_launch ? b(kXl) : nullptr;
+    bio.s0 = io.s0 ? b(kS0) : nullptr, bio.traj = n_save ? b(kTr) : nullptr;
     for (int lo = 0; lo < n; lo += nb) {
-        const int c = std::min(nb, n - lo);
+        const int c = bio.n = std::min(nb, n - lo);
         // array k's rows of c rays from / to the caller's array h (rows of n rays, from ray lo)
         auto gather = [&](int k, const double *h) -> int {
             if (!h) return 0;
@@ -748,16 +752,36 @@ static int trace_batched(torj_plasma_t p, const torj_trace_cfg *cfg, int n, int 
             HIPCK(hipMemcpy2DAsync(h + lo, (size_t)n * D, b(k), c * D, c * D, rows[k], hipMemcpyDeviceToDevice, s));
             return 0;
         };
-        if (gather(kX0, x0) || gather(kN0, N0) || gather(kXl, x_launch) || gather(kW, weights) || gather(kS0, s0))
+        if (gather(kX0, io.x0) || gather(kN0, io.N0) || gather(kXl, io.x_launch) || gather(kW, io.weights) ||
+            gather(kS0, io.s0))
             return -1;
-        if (trace_device_one(p, cfg, c, b(kX0), b(kN0), weights ? b(kW) : nullptr, n_psi, grid,
-                             x_launch ? b(kXl) : nullptr, s0 ? b(kS0) : nullptr, b(kSt), bstat, bsteps, dP, b(kP),
-                             n_save ? b(kTr) : nullptr, counters, s))
-            return -1;
-        if (scatter(state, kSt) || scatter(Pdep, kP) || scatter(n_save ? traj : nullptr, kTr)) return -1;
-        HIPCK(hipMemcpyAsync(status + lo, bstat, c * sizeof(int), hipMemcpyDeviceToDevice, s));
-        HIPCK(hipMemcpyAsync(steps + lo, bsteps, c * sizeof(int), hipMemcpyDeviceToDevice, s));
+        if (trace_device_one(p, cfg, bio, n_psi, s)) return -1;
+        if (scatter(io.state, kSt) || scatter(io.P_dep, kP) || scatter(n_save ? io.traj : nullptr, kTr)) return -1;
+        HIPCK(hipMemcpyAsync(io.status + lo, bio.status, c * sizeof(int), hipMemcpyDeviceToDevice, s));
+        HIPCK(hipMemcpyAsync(io.steps + lo, bio.steps, c * sizeof(int), hipMemcpyDeviceToDevice, s));
     }
     return 0;
+}
+
+// a trace on the caller's stream, whole or in ray batches (torj_trace_device_ex and every layer above it)
+static int trace_device(torj_plasma_t p, const torj_trace_cfg *cfg, const RayIO &io, int n_psi, void *stream) {
+    if (!p || !cfg) return fail("bad plasma handle or cfg");
+    if (io.n <= 0) return 0;
+    return on_caller_stream(p, stream, [&](hipStream_t s) {
+        if (p->timing) p->timing_calls++;
+        const bool fit = n_psi >= 2 && io.psi_grid && io.dP_shell && cfg->deposition == 1;
+        // TORJ_SPLIT_BATCH=R (read per call; fixed-step absorbing beams): trace in
+        // contiguous batches of R rays (a multiple of 64), each its own pipeline
+        const long sb_rays =
+            (cfg->integrator == 0 && cfg->absorption >= 1) ? env_long("TORJ_SPLIT_BATCH", 0) / 64 * 64 : 0;
+        if ((fit || sb_rays > 0) && cfg->n_steps > 0 && launch_ptrs(io).rays) {
+            const size_t per_ray =
+                fit ? fit_bytes_per_ray((size_t)cfg->n_steps + 2, (size_t)n_psi, cfg->integrator == 1) : 0;
+            if (ensure_device(p)) return -1;
+            const size_t nb = batch_rays((size_t)io.n, per_ray, ws_budget(p), sb_rays);
+            if (nb < (size_t)io.n) return trace_batched(p, cfg, io, (int)nb, n_psi, s);
+        }
+        return trace_device_one(p, cfg, io, n_psi, s);
+    });
 }
 #endif  // TORJ_LAUNCH_PLAN_ONLY
