@@ -45,7 +45,9 @@ extern "C" {
                                torj_ray_entry_beams_plasmas_gpu, torj_ray_entry_beams_plasmas_device;
                                still 8 (four more symbols, nothing changed): torj_plasma_update,
                                torj_plasma_update_from_coefs, torj_plasma_update_profiles,
-                               torj_plasma_get_cell_table */
+                               torj_plasma_get_cell_table;
+                               still 8 (three more symbols, nothing changed): torj_plasma_update_gpu,
+                               torj_plasma_update_profiles_gpu, torj_plasma_update_device */
 
 /* per-ray status codes (replace the reference's @assert / unhandled returns) */
 enum torj_status {
@@ -163,6 +165,55 @@ int torj_plasma_update_from_coefs(torj_plasma_t p, double R1, double Rn, double 
  * equilibrium came as coefficients. */
 int torj_plasma_update_profiles(torj_plasma_t p, int n_prof, const double *psi_prof,
                                 const double *ne_prof, const double *Te_prof, void *stream);
+/* ---- ... with the 2-D spline coefficients built on the device ------------------
+ * The three calls below do what torj_plasma_update and torj_plasma_update_profiles
+ * do, but the six (or two) 2-D B-spline prefilters, the host's ~2 ms per plasma at
+ * 129 x 129 nodes, run on the GPU in `stream`'s order, ahead of k_cell_table:
+ * make_2d_prof_spline's node map, a prefilter along R and one along Z, the host's
+ * operation sequences under IEEE arithmetic, so the device coefficients are bit for
+ * bit the host's.  The host keeps the 1-D parts (the profiles' resampling, log and
+ * 1-D prefilter, the volume spline, psi_prof_max, the box) with the functions the
+ * host updates use.
+ *
+ * Checks and refusals are torj_plasma_update's (the message starts with the
+ * function's name and names the argument); further refusals, which also leave the
+ * handle as it was: no usable GPU for the handle's device, and a profiles-only call
+ * on a handle whose equilibrium came as coefficients.  A handle never used on the
+ * GPU gets its device state first.  Host arrays are consumed before the call
+ * returns (copied in stream order into a grow-only staging buffer of the handle:
+ * 0.53 MB for a full update at 129 x 129, about 1 KB for a profiles-only one);
+ * nothing synchronises.  The stream rules are torj_plasma_update's.  The handle
+ * keeps the psi node map on the device for later profiles-only calls (a handle
+ * that only has the host copy uploads it on first need).  Replicas get the built
+ * coefficients by a device copy (a peer copy across devices) behind the build,
+ * then rebuild their own cell tables.
+ *
+ * HOST READS SYNCHRONISE.  After one of these calls the handle's host copy of the
+ * coefficients (and, after torj_plasma_update_device, of psi_norm_data) is stale.
+ * The host readers -- torj_plasma_get_coefs, the host torj_ray_entry, the host
+ * torj_plasma_update_profiles, and the creation of replicas by torj_trace_beam --
+ * first wait for the build's event and download the copy, once; a later host
+ * update (torj_plasma_update, torj_plasma_update_from_coefs) replaces it without a
+ * download.  The GPU entries (torj_ray_entry_gpu, the traces, torj_eval_plasma)
+ * never read the host copy. */
+/* torj_plasma_update's arguments; all arrays are host arrays */
+int torj_plasma_update_gpu(torj_plasma_t p, const double *R_coords, const double *Z_coords,
+                           const double *psi_norm_data, int n_prof, const double *psi_prof,
+                           const double *ne_prof, const double *Te_prof, const double *Br_data,
+                           const double *Bz_data, const double *Bphi_data, int n_eq,
+                           const double *eqt1d_psi_norm, const double *eqt1d_volume, void *stream);
+/* torj_plasma_update_profiles' arguments */
+int torj_plasma_update_profiles_gpu(torj_plasma_t p, int n_prof, const double *psi_prof,
+                                    const double *ne_prof, const double *Te_prof, void *stream);
+/* torj_plasma_update_gpu with psi_norm_data, Br_data, Bz_data, Bphi_data (nR x nZ,
+ * R fastest) as device pointers on the handle's device, read in `stream`'s order:
+ * they must stay valid and unchanged until the stream has passed the call.
+ * R_coords, Z_coords, the profiles and the volume table stay host arrays. */
+int torj_plasma_update_device(torj_plasma_t p, const double *R_coords, const double *Z_coords,
+                              const double *psi_norm_data, int n_prof, const double *psi_prof,
+                              const double *ne_prof, const double *Te_prof, const double *Br_data,
+                              const double *Bz_data, const double *Bphi_data, int n_eq,
+                              const double *eqt1d_psi_norm, const double *eqt1d_volume, void *stream);
 /* the per-cell power table as it stands on the device: (nR-1) x (nZ-1) cells, R
  * fastest, 96 doubles each (field slot f of Br, Bphi, Bz, ln ne, ln Te, psi at
  * f * 16, the coefficient of sZ^j sR^i at j * 4 + i, per metre).  Waits for the

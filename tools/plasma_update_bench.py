@@ -8,17 +8,24 @@ the reference deposition on 1 000 shells, rays device-resident (DESIGN.md 3.2d's
 workload).  Timed, alternating, after a warm-up pair:
   (a) torj_plasma_destroy + torj_plasma_create of all 24, then the launch -- the only way
       to put new physics on the GPU before torj_plasma_update, hence the baseline;
-  (b) torj_plasma_update of the 24 pooled handles on the launch's stream, then the launch.
+  (b) torj_plasma_update of the 24 pooled handles on the launch's stream, then the launch;
+  (c) torj_plasma_update_gpu of the same handles -- the 2-D prefilters on the device, in the
+      stream's order -- then the launch, alternating with (b).
 Each reports the wall time from the first refill call to the end of a stream
 synchronisation, the host time of the refill calls alone, and torj_timing's trace / post
 milliseconds of the launch.  The launch's outputs are the same bits in (a) and (b)
-(asserted), and (b) must be faster than (a) in every pair (asserted).
+(asserted), and (b) must be faster than (a) in every pair (asserted).  (b) and (c) give the
+same bits on the pool and on the split leg (asserted); at 129 x 129 (c) must be faster than
+(b) in every pair of the pool leg (asserted), the other figures are recorded.
 
 Also one handle on the split path (torj_set_sched(p, 3, 0), 4 096 rays, 2 000 steps): (a)
 destroy + create + trace, (b) update + trace; there the cell table an update builds on the
 device differs from the host's in rounding, and the largest output difference is recorded.
 
-    python tools/plasma_update_bench.py --out profiles/r15/plasma_update_bench.json
+Last, one 129 x 129 handle in a profiles-only loop: torj_plasma_update_profiles against
+torj_plasma_update_profiles_gpu, each followed by a stream synchronisation (recorded).
+
+    python tools/plasma_update_bench.py --out profiles/r16/plasma_update_bench.json
 """
 import argparse
 import ctypes
@@ -110,6 +117,23 @@ def main():
         return dict(pairs=pairs, wall_ratio_a_over_b=ratios, b_faster_in_every_pair=True,
                     max_abs_output_difference_a_vs_b=diff)
 
+    def pairs_bc(run_b, run_c, out, what, c_must_win):
+        """(c) against (b), the same way; their outputs must be the same bits"""
+        run_b(), run_c()
+        keep = {k: v.clone() for k, v in out.items()}
+        run_b()
+        diff = {k: float((out[k].double() - keep[k].double()).abs().max()) for k in out}  # (b) against (c)
+        assert not any(diff.values()), f"{what}: the outputs differ between (b) and (c): {diff}"
+        pairs = [dict(b=run_b(), c=run_c()) for _ in range(args.pairs)]
+        ratios = [p["b"]["wall_ms"] / p["c"]["wall_ms"] for p in pairs]
+        print(what + " " + " ".join(f"[b {p['b']['wall_ms']:.1f} (refill {p['b']['refill_host_ms']:.1f}) "
+                                    f"c {p['c']['wall_ms']:.1f} (refill {p['c']['refill_host_ms']:.1f}) ms]"
+                                    for p in pairs), flush=True)
+        if c_must_win:
+            assert all(r > 1.0 for r in ratios), f"{what}: the device build is not faster in every pair"
+        return dict(pairs=pairs, wall_ratio_b_over_c=ratios, c_faster_in_every_pair=all(r > 1.0 for r in ratios),
+                    c_faster_asserted=c_must_win, same_bits_b_and_c=True)
+
     results = []
     for G in (int(v) for v in args.grids.split(",")):
         eqs = [S.circular_tokamak(nR=G, nZ=G, Te0=1500.0 + 200.0 * j, ne_scale=0.6 + 0.03 * j) for j in range(N_POOL)]
@@ -149,6 +173,13 @@ def main():
         pool = pairs_of(lambda: timed(recreate_pool, launch_pool, lambda: hs[0]),
                         lambda: timed(update_pool, launch_pool, lambda: hs[0]), o, f"G={G} pool")
         assert not any(pool["max_abs_output_difference_a_vs_b"].values()), "the pool's outputs differ between (a) and (b)"
+
+        def update_pool_gpu():
+            for j in range(N_POOL):
+                hs[j].update_gpu(*pargs[j], stream=stream.cuda_stream or None)
+
+        pool_bc = pairs_bc(lambda: timed(update_pool, launch_pool, lambda: hs[0]),
+                           lambda: timed(update_pool_gpu, launch_pool, lambda: hs[0]), o, f"G={G} pool (b, c)", G == 129)
         # ---- one handle on the split path ----
         pos, dirs, w = (a[:N_SPLIT] for a in fan(34))
         assert len(w) == N_SPLIT
@@ -177,8 +208,34 @@ def main():
 
         split = pairs_of(lambda: timed(recreate_one, launch_split, lambda: one[0]),
                          lambda: timed(update_one, launch_split, lambda: one[0]), so, f"G={G} split")
-        results.append(dict(grid=[G, G], pool=dict(n_plasmas=N_POOL, n_beams=N_POOL, n_rays=n, **pool),
-                            split=dict(n_rays=N_SPLIT, sched_mode=3, **split)))
+
+        def update_one_gpu():
+            one[0].update_gpu(*pargs[0], stream=stream.cuda_stream or None)
+
+        split_bc = pairs_bc(lambda: timed(update_one, launch_split, lambda: one[0]),
+                            lambda: timed(update_one_gpu, launch_split, lambda: one[0]), so, f"G={G} split (b, c)", False)
+        res = dict(grid=[G, G], pool=dict(n_plasmas=N_POOL, n_beams=N_POOL, n_rays=n, **pool),
+                   split=dict(n_rays=N_SPLIT, sched_mode=3, **split), pool_b_vs_c=pool_bc, split_b_vs_c=split_bc)
+        if G == 129:  # a transport loop's step: new profiles on one handle, to the end of a synchronisation
+            prof = [(eq["psi_prof"], eq["ne_prof"], eq["Te_prof"]) for eq in eqs]
+
+            def loop(call):
+                stream.synchronize()
+                ms = []
+                for j in range(N_POOL):
+                    t0 = time.perf_counter()
+                    call(*prof[j], stream=stream.cuda_stream or None)
+                    t1 = time.perf_counter()
+                    stream.synchronize()
+                    ms.append(((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3))
+                return dict(host_ms_median=float(np.median([m[0] for m in ms[1:]])),
+                            to_sync_ms_median=float(np.median([m[1] for m in ms[1:]])), calls=N_POOL - 1)
+
+            loop(one[0].update_profiles), loop(one[0].update_profiles_gpu)  # warm-up
+            res["profiles_only_loop"] = dict(update_profiles=loop(one[0].update_profiles),
+                                             update_profiles_gpu=loop(one[0].update_profiles_gpu))
+            print(f"G={G} profiles-only: {res['profiles_only_loop']}", flush=True)
+        results.append(res)
         for P in hs + one:
             destroy(P)
 
@@ -188,6 +245,7 @@ def main():
                plasmas="plasma j: Te0 = 1500 + 200 j eV, ne_scale = 0.6 + 0.03 j, on G x G nodes",
                a="torj_plasma_destroy + torj_plasma_create of every handle, then the launch (baseline)",
                b="torj_plasma_update of the live handles on the launch's stream, then the launch",
+               c="torj_plasma_update_gpu of the live handles on the launch's stream, then the launch",
                wall_ms="from the first refill call to the end of the stream synchronisation after the launch",
                results=results)
     if args.out:
@@ -195,7 +253,10 @@ def main():
         with open(args.out, "w") as fh:
             fh.write(json.dumps(doc, indent=1) + "\n")
     print(json.dumps(dict(plasma_update_bench=[dict(grid=r["grid"], pool=r["pool"]["wall_ratio_a_over_b"],
-                                                    split=r["split"]["wall_ratio_a_over_b"]) for r in results])))
+                                                    split=r["split"]["wall_ratio_a_over_b"],
+                                                    pool_b_over_c=r["pool_b_vs_c"]["wall_ratio_b_over_c"],
+                                                    split_b_over_c=r["split_b_vs_c"]["wall_ratio_b_over_c"])
+                                               for r in results])))
 
 
 if __name__ == "__main__":

@@ -25,9 +25,23 @@ static int beam_replicas(torj_plasma_s *p, int n_gpus, bool same) {
     HIPCK(hipGetDeviceCount(&ndev));
     if (n_gpus < 1 || (!same && n_gpus > ndev))
         return fail("n_gpus = %d, but %d HIP devices are visible", n_gpus, ndev);
+    // a replica that has no device state yet gets it from its host copy of the coefficients: after a
+    // device-side build the base handle's copy is downloaded first (mirror_sync), for the new
+    // replicas (a changed placement makes them all new) and for those the build found without device state
+    auto dev_of = [&](size_t k) { return same ? p->device : (p->device + (int)k) % ndev; };
+    bool need = std::max<size_t>(1, p->replicas.size()) < (size_t)n_gpus;
+    for (size_t k = 1; k < p->replicas.size(); k++) {
+        const torj_plasma_s *q = p->replicas[k];
+        need = need || q->device != dev_of(k) || (q->coef_stale && !q->d_flags);
+    }
+    if (need && mirror_sync(p)) return -1;
     std::lock_guard<std::mutex> lk(p->mu);
     if (p->replicas.empty()) p->replicas.push_back(p);
-    auto dev_of = [&](size_t k) { return same ? p->device : (p->device + (int)k) % ndev; };
+    for (size_t k = 1; need && k < p->replicas.size(); k++)
+        if (p->replicas[k]->coef_stale && !p->replicas[k]->d_flags) {
+            p->replicas[k]->coef = p->coef;
+            p->replicas[k]->coef_stale = false;
+        }
     for (size_t k = 1; k < p->replicas.size(); k++)
         if (p->replicas[k]->device != dev_of(k)) {  // placement changed: rebuild them all
             for (ncclComm_t c : p->comms) (void)ncclCommDestroy(c);

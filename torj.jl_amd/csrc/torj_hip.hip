@@ -11,6 +11,8 @@
 //   torj_k_beams.hpp    the multi-beam forms of k_trace and the kernels around it,
 //                       also for beams that go through differing plasmas
 //   torj_celltab.hpp    the cell table rebuilt on the device (torj_plasma_update*)
+//   torj_coefbuild.hpp  the node coefficients built on the device (torj_plasma_update_gpu,
+//                       _profiles_gpu, _device): one prefilter line, one profile node, their kernels
 //   torj_host_util.hpp  fail / HIPCK, the environment knobs, GrowBuf
 //   torj_plasma.hpp     the plasma handle and its device state
 //   torj_fan.hpp        quadrature nodes and the launch fan
@@ -49,6 +51,7 @@ using namespace torj;
 #include "torj_k_points.hpp"
 #include "torj_k_beams.hpp"
 #include "torj_celltab.hpp"
+#include "torj_coefbuild.hpp"
 #include "torj_plasma.hpp"
 #include "torj_fan.hpp"
 #include "torj_split.hpp"
@@ -220,11 +223,8 @@ int torj_abs_al_init(int n) {
 static void prof2d_coefs(int nR, int nZ, const double *psi_norm, int n_prof, const double *psi_prof,
                          const double *prof, std::vector<double> &c2) {
     const size_t nd = (size_t)nR * nZ;
-    std::vector<double> pr = uniform_range(psi_prof[0], psi_prof[n_prof - 1], n_prof);
-    std::vector<double> p2(n_prof), c1(n_prof + 2), d2(nd);
-    natcubic(n_prof, psi_prof, prof, n_prof, pr.data(), p2.data());
-    for (double &v : p2) v = std::log(v);
-    bspl1d_prefilter(n_prof, p2.data(), 1, c1.data(), 1);
+    std::vector<double> c1, d2(nd);
+    prof1d_coefs(n_prof, psi_prof, prof, c1);
     for (size_t k = 0; k < nd; k++)
         d2[k] = bspl1d_eval(c1, n_prof, psi_prof[0], psi_prof[n_prof - 1], psi_norm[k]);
     bspl2d_prefilter(nR, nZ, d2.data(), c2.data());
@@ -280,8 +280,13 @@ static int plasma_from_coefs(torj_plasma_s *p, int nR, int nZ, double R1, double
 // the device half, on one handle or replica whose device state exists: the new
 // coefficients into d_coef (from pageable memory, consumed when the copy returns:
 // beams_upload's rule), then d_cellp rebuilt from them, both in `s`'s order
+static int cell_table_enqueue(torj_plasma_s *q, hipStream_t s);
 static int plasma_update_enqueue(torj_plasma_s *q, hipStream_t s) {
     HIPCK(hipMemcpyAsync(q->d_coef, q->coef.data(), q->coef.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    return cell_table_enqueue(q, s);
+}
+// d_cellp rebuilt from d_coef in `s`'s order
+static int cell_table_enqueue(torj_plasma_s *q, hipStream_t s) {
     const long n = (long)(q->g.nR - 1) * (q->g.nZ - 1) * kCellNS;
     hipLaunchKernelGGL(k_cell_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q->d_coef, q->g, q->d_cellp);
     HIPCK(hipGetLastError());
@@ -303,9 +308,12 @@ static int plasma_adopt(torj_plasma_s *p, torj_plasma_s &fresh, void *stream) {
             q->n_vol = fresh.n_vol, q->v1 = fresh.v1, q->vn = fresh.vn;
             q->vol_coef = fresh.vol_coef;
             q->psi_prof_max = fresh.psi_prof_max;
+            q->coef_stale = false;  // (a device-side build's mirror: replaced, not downloaded)
             if (q->d_flags) live.push_back(q);
         }
         p->psi_nodes.swap(fresh.psi_nodes);
+        p->psi_stale = false;
+        p->d_psi_valid = false;
     }
     int rc = 0;
     for (torj_plasma_s *q : live) {
@@ -330,6 +338,174 @@ static int plasma_adopt(torj_plasma_s *p, torj_plasma_s &fresh, void *stream) {
     }
     if (live.size() > 1 || (live.size() == 1 && live[0] != p)) (void)hipSetDevice(p->device);
     return rc;
+}
+
+// ===========================================================================
+// torj_plasma_update_gpu, _profiles_gpu, _device: the 2-D coefficients built on
+// the device (torj_coefbuild.hpp)
+// ===========================================================================
+// (cb_field_slot's nibbles against kFieldSlot itself: tests/native/coefbuild_host.hip cb_slots_ok)
+static_assert(F_PSI == 5 && F_LNNE == 3 && F_LNTE == 4 && F_BR == 0 && F_BZ == 2 && F_BPHI == 1,
+              "cb_field_slot's nibbles are kFieldSlot's values");
+
+// The 1-D host state of an update, complete before the handle is touched: the two ln-profile
+// splines (today's host functions: glibc's log and the device's differ in the last bit),
+// psi_prof_max, and for a full update the box and the volume spline.
+struct Update1D {
+    bool full = false;
+    int n_prof = 0;
+    double x1 = 0, xn = 0, psi_prof_max = 0;
+    std::vector<double> c1_ne, c1_te;
+    Grid g{};
+    int n_vol = 0;
+    double v1 = 0, vn = 0;
+    std::vector<double> vol_coef;
+};
+static void update1d_profiles(Update1D &u, int n_prof, const double *psi_prof, const double *ne_prof,
+                              const double *Te_prof) {
+    u.n_prof = n_prof;
+    u.x1 = psi_prof[0], u.xn = psi_prof[n_prof - 1];
+    prof1d_coefs(n_prof, psi_prof, ne_prof, u.c1_ne);
+    prof1d_coefs(n_prof, psi_prof, Te_prof, u.c1_te);
+    u.psi_prof_max = *std::max_element(psi_prof, psi_prof + n_prof);
+}
+static void update1d_full(Update1D &u, int nR, int nZ, const double *R, const double *Z, int n_eq,
+                          const double *eq_psi, const double *eq_vol) {
+    u.full = true;
+    u.g = grid_box(nR, nZ, R[0], R[nR - 1], Z[0], Z[nZ - 1]);
+    // volume_psi_spline (src/plasma.jl:42-44), as plasma_from_maps
+    std::vector<double> pr = uniform_range(eq_psi[0], eq_psi[n_eq - 1], n_eq), v2(n_eq);
+    natcubic(n_eq, eq_psi, eq_vol, n_eq, pr.data(), v2.data());
+    u.n_vol = n_eq;
+    u.v1 = eq_psi[0];
+    u.vn = eq_psi[n_eq - 1];
+    u.vol_coef.assign(n_eq + 2, 0.0);
+    bspl1d_prefilter(n_eq, v2.data(), 1, u.vol_coef.data(), 1);
+}
+
+// where a build's node maps are: host arrays (psi, Br, Bz, Bphi; consumed before the call returns),
+// device arrays read in stream order, or neither (profiles only: the handle's own psi nodes)
+struct BuildMaps {
+    const double *host[4] = {nullptr, nullptr, nullptr, nullptr};
+    const double *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+// The build on `s`: staging copies, the three kernels into d_coef, k_cell_table; ev_B at its end.
+// Then each live replica's device copy of d_coef (a peer copy across devices) and its own
+// k_cell_table on its own stream, behind ev_B; `s` waits for those copies, so that a later
+// build on it cannot overwrite d_coef under them.
+static int plasma_build_enqueue(torj_plasma_s *p, const Update1D &u, const BuildMaps &m, hipStream_t s,
+                                const std::vector<torj_plasma_s *> &live) {
+    const int nR = p->g.nR, nZ = p->g.nZ;
+    const size_t nd = (size_t)nR * nZ, ncp = (size_t)std::max(nR, nZ), n1 = (size_t)u.n_prof + 2;
+    double *stg = (double *)p->cbuild.d;
+    // the small block: pivots and the two 1-D splines, packed into one copy from pageable memory
+    std::vector<double> small(ncp + 2 * n1, 0.0);
+    cb_pivots(std::max(nR, nZ) - 2, small.data());
+    std::copy(u.c1_ne.begin(), u.c1_ne.end(), small.begin() + ncp);
+    std::copy(u.c1_te.begin(), u.c1_te.end(), small.begin() + ncp + n1);
+    HIPCK(hipMemcpyAsync(stg, small.data(), small.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    CoefBuild a{};
+    a.coef = p->d_coef;
+    a.cp = stg, a.c1_ne = stg + ncp, a.c1_te = stg + ncp + n1;
+    a.psi = p->d_psi;
+    a.x1 = u.x1, a.xn = u.xn, a.n_prof = u.n_prof, a.nR = nR, a.nZ = nZ;
+    a.f0 = u.full ? 0 : 1, a.nf = u.full ? 6 : 2;
+    if (m.host[0]) {
+        double *maps = stg + small.size();
+        HIPCK(hipMemcpyAsync(p->d_psi, m.host[0], nd * sizeof(double), hipMemcpyHostToDevice, s));
+        for (int k = 1; k < 4; k++)
+            HIPCK(hipMemcpyAsync(maps + (size_t)(k - 1) * nd, m.host[k], nd * sizeof(double), hipMemcpyHostToDevice, s));
+        a.Br = maps, a.Bz = maps + nd, a.Bphi = maps + 2 * nd;
+    } else if (m.dev[0]) {
+        HIPCK(hipMemcpyAsync(p->d_psi, m.dev[0], nd * sizeof(double), hipMemcpyDeviceToDevice, s));
+        a.Br = m.dev[1], a.Bz = m.dev[2], a.Bphi = m.dev[3];
+    } else if (!p->d_psi_valid) {  // profiles only, first need: the host copy of the psi nodes
+        HIPCK(hipMemcpyAsync(p->d_psi, p->psi_nodes.data(), nd * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    p->d_psi_valid = true;
+    const long n_nodes = (long)nd * a.nf;
+    hipLaunchKernelGGL(k_coef_nodes, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_coef_prefilter, dim3((unsigned)nblocks(nZ * a.nf, 64)), dim3(64), 0, s, a, false);
+    hipLaunchKernelGGL(k_coef_prefilter, dim3((unsigned)nblocks((nR + 2) * a.nf, 64)), dim3(64), 0, s, a, true);
+    HIPCK(hipGetLastError());
+    if (cell_table_enqueue(p, s)) return -1;
+    if (!p->ev_B) HIPCK(hipEventCreateWithFlags(&p->ev_B, hipEventDisableTiming));
+    HIPCK(hipEventRecord(p->ev_B, s));
+    // the host-pointer entries run on the handle's own stream: it waits for this build
+    if (s != p->stream) HIPCK(hipStreamWaitEvent(p->stream, p->ev_B, 0));
+    for (torj_plasma_s *q : live) {
+        if (q == p) continue;
+        const size_t bytes = p->coef.size() * sizeof(double);
+        HIPCK(hipSetDevice(q->device));
+        HIPCK(hipStreamWaitEvent(q->stream, p->ev_B, 0));
+        if (q->device == p->device)
+            HIPCK(hipMemcpyAsync(q->d_coef, p->d_coef, bytes, hipMemcpyDeviceToDevice, q->stream));
+        else
+            HIPCK(hipMemcpyPeerAsync(q->d_coef, q->device, p->d_coef, p->device, bytes, q->stream));
+        if (cell_table_enqueue(q, q->stream)) return -1;
+        if (!q->ev_U) HIPCK(hipEventCreateWithFlags(&q->ev_U, hipEventDisableTiming));
+        HIPCK(hipEventRecord(q->ev_U, q->stream));
+        HIPCK(hipSetDevice(p->device));
+        HIPCK(hipStreamWaitEvent(s, q->ev_U, 0));
+    }
+    return 0;
+}
+
+// The device-side counterpart of plasma_adopt.  `who` names the entry in messages.  The handle gets
+// its device state if it has none; the staging buffers are sized; then the 1-D state becomes the
+// handle's and its replicas', their host coefficients (and, for device maps, the psi nodes) are
+// marked stale, and the build is enqueued on the caller's stream.  Nothing waits for the device.
+static int plasma_build(torj_plasma_s *p, const char *who, const Update1D &u, const BuildMaps &m, void *stream) {
+    const size_t nd = (size_t)p->g.nR * p->g.nZ;
+    std::vector<torj_plasma_s *> live;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        const size_t need = (size_t)std::max(p->g.nR, p->g.nZ) + 2 * ((size_t)u.n_prof + 2) + (m.host[0] ? 3 * nd : 0);
+        if (p->cbuild.reserve(need * sizeof(double))) return -1;
+        if (!p->d_psi) HIPCK(hipMalloc(&p->d_psi, nd * sizeof(double)));
+        for (size_t k = 0; k < std::max<size_t>(1, p->replicas.size()); k++) {
+            torj_plasma_s *q = k == 0 ? p : p->replicas[k];
+            if (u.full) {
+                q->g = u.g;
+                q->n_vol = u.n_vol, q->v1 = u.v1, q->vn = u.vn;
+                q->vol_coef = u.vol_coef;
+            }
+            q->psi_prof_max = u.psi_prof_max;
+            q->coef_stale = true;
+            if (q->d_flags) live.push_back(q);
+        }
+        if (m.host[0]) {
+            p->psi_nodes.assign(m.host[0], m.host[0] + nd);
+            p->psi_stale = false;
+        } else if (m.dev[0]) {
+            p->psi_stale = true;
+        }
+    }
+    const int rc = on_caller_stream(p, stream, [&](hipStream_t s) { return plasma_build_enqueue(p, u, m, s, live); });
+    if (live.size() > 1) (void)hipSetDevice(p->device);
+    if (rc) return fail("%s: %s", who, std::string(g_err).c_str());
+    return 0;
+}
+
+// the checks the three entries share, before anything else: the arguments by name (build_checks), then a
+// usable GPU (build_device: the handle's device state, created here on its first GPU use)
+struct NamedPtr {
+    const char *name;
+    const void *ptr;
+};
+static int build_checks(torj_plasma_s *p, const char *who, const NamedPtr *args, size_t n_args, int n_prof,
+                        const int *n_eq) {
+    if (!p) return fail("%s: p is NULL", who);
+    for (size_t k = 0; k < n_args; k++)
+        if (!args[k].ptr) return fail("%s: %s is NULL", who, args[k].name);
+    if (n_prof < 2) return fail("%s: n_prof = %d < 2", who, n_prof);
+    if (n_eq && *n_eq < 2) return fail("%s: n_eq = %d < 2", who, *n_eq);
+    return 0;
+}
+static int build_device(torj_plasma_s *p, const char *who) {
+    if (ensure_device(p)) return fail("%s: no usable GPU for the handle (%s)", who, std::string(g_err).c_str());
+    return 0;
 }
 
 extern "C" {
@@ -421,6 +597,7 @@ int torj_plasma_update_profiles(torj_plasma_t p, int n_prof, const double *psi_p
     if (!Te_prof) return fail("torj_plasma_update_profiles: Te_prof is NULL");
     if (n_prof < 2) return fail("torj_plasma_update_profiles: n_prof = %d < 2", n_prof);
     const int nR = p->g.nR, nZ = p->g.nZ;
+    if (mirror_sync(p)) return -1;  // after a device-side build: the coefficients and the psi nodes it left there
     torj_plasma_s fresh;
     {
         std::lock_guard<std::mutex> lk(p->mu);
@@ -445,6 +622,61 @@ int torj_plasma_update_profiles(torj_plasma_t p, int n_prof, const double *psi_p
     }
     fresh.psi_prof_max = *std::max_element(psi_prof, psi_prof + n_prof);
     return plasma_adopt(p, fresh, stream);
+}
+
+// torj_plasma_update with the six 2-D prefilters on the device; all arrays are host arrays
+int torj_plasma_update_gpu(torj_plasma_t p, const double *R, const double *Z, const double *psi_norm, int n_prof,
+                           const double *psi_prof, const double *ne_prof, const double *Te_prof, const double *Br,
+                           const double *Bz, const double *Bphi, int n_eq, const double *eq_psi,
+                           const double *eq_vol, void *stream) {
+    const char *who = "torj_plasma_update_gpu";
+    const NamedPtr args[] = {{"R_coords", R},     {"Z_coords", Z},   {"psi_norm_data", psi_norm}, {"psi_prof", psi_prof},
+                             {"ne_prof", ne_prof}, {"Te_prof", Te_prof}, {"Br_data", Br},          {"Bz_data", Bz},
+                             {"Bphi_data", Bphi}, {"eqt1d_psi_norm", eq_psi}, {"eqt1d_volume", eq_vol}};
+    if (build_checks(p, who, args, sizeof args / sizeof *args, n_prof, &n_eq) || build_device(p, who)) return -1;
+    Update1D u;
+    update1d_profiles(u, n_prof, psi_prof, ne_prof, Te_prof);
+    update1d_full(u, p->g.nR, p->g.nZ, R, Z, n_eq, eq_psi, eq_vol);
+    BuildMaps m;
+    m.host[0] = psi_norm, m.host[1] = Br, m.host[2] = Bz, m.host[3] = Bphi;
+    return plasma_build(p, who, u, m, stream);
+}
+
+// ... with psi_norm_data, Br_data, Bz_data, Bphi_data in device memory, read in `stream`'s order
+int torj_plasma_update_device(torj_plasma_t p, const double *R, const double *Z, const double *d_psi_norm, int n_prof,
+                              const double *psi_prof, const double *ne_prof, const double *Te_prof,
+                              const double *d_Br, const double *d_Bz, const double *d_Bphi, int n_eq,
+                              const double *eq_psi, const double *eq_vol, void *stream) {
+    const char *who = "torj_plasma_update_device";
+    const NamedPtr args[] = {{"R_coords", R},     {"Z_coords", Z},   {"psi_norm_data", d_psi_norm}, {"psi_prof", psi_prof},
+                             {"ne_prof", ne_prof}, {"Te_prof", Te_prof}, {"Br_data", d_Br},           {"Bz_data", d_Bz},
+                             {"Bphi_data", d_Bphi}, {"eqt1d_psi_norm", eq_psi}, {"eqt1d_volume", eq_vol}};
+    if (build_checks(p, who, args, sizeof args / sizeof *args, n_prof, &n_eq) || build_device(p, who)) return -1;
+    Update1D u;
+    update1d_profiles(u, n_prof, psi_prof, ne_prof, Te_prof);
+    update1d_full(u, p->g.nR, p->g.nZ, R, Z, n_eq, eq_psi, eq_vol);
+    BuildMaps m;
+    m.dev[0] = d_psi_norm, m.dev[1] = d_Br, m.dev[2] = d_Bz, m.dev[3] = d_Bphi;
+    return plasma_build(p, who, u, m, stream);
+}
+
+// torj_plasma_update_profiles with the two 2-D prefilters on the device, from the psi nodes kept there
+int torj_plasma_update_profiles_gpu(torj_plasma_t p, int n_prof, const double *psi_prof, const double *ne_prof,
+                                    const double *Te_prof, void *stream) {
+    const char *who = "torj_plasma_update_profiles_gpu";
+    const NamedPtr args[] = {{"psi_prof", psi_prof}, {"ne_prof", ne_prof}, {"Te_prof", Te_prof}};
+    if (build_checks(p, who, args, sizeof args / sizeof *args, n_prof, nullptr)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->psi_nodes.empty() && !p->d_psi_valid)
+            return fail("%s: the handle has no psi_norm_data (its equilibrium came as coefficients: "
+                        "torj_plasma_create_from_coefs / torj_plasma_update_from_coefs); use "
+                        "torj_plasma_update_from_coefs", who);
+    }
+    if (build_device(p, who)) return -1;
+    Update1D u;
+    update1d_profiles(u, n_prof, psi_prof, ne_prof, Te_prof);
+    return plasma_build(p, who, u, BuildMaps{}, stream);
 }
 
 int torj_plasma_get_cell_table(torj_plasma_t p, double *out) {
@@ -483,6 +715,9 @@ int torj_plasma_destroy(torj_plasma_t p) {
     if (p->ev_Nin) (void)hipEventDestroy(p->ev_Nin);
     if (p->ev_Nout) (void)hipEventDestroy(p->ev_Nout);
     if (p->ev_U) (void)hipEventDestroy(p->ev_U);
+    if (p->ev_B) (void)hipEventDestroy(p->ev_B);
+    if (p->cbuild.d) (void)hipFree(p->cbuild.d);
+    if (p->d_psi) (void)hipFree(p->d_psi);
     if (p->sched.d) (void)hipFree(p->sched.d);
     if (p->fit.d) (void)hipFree(p->fit.d);
     if (p->d_flags) (void)hipFree(p->d_flags);
@@ -510,6 +745,7 @@ int torj_plasma_destroy(torj_plasma_t p) {
 
 int torj_plasma_get_coefs(torj_plasma_t p, int field, double *out) {
     if (!p || field < 0 || field > 5) return fail("bad plasma handle or field index");
+    if (mirror_sync(p)) return -1;
     const size_t nodes = (size_t)(p->g.nR + 2) * (p->g.nZ + 2);
     for (size_t k = 0; k < nodes; k++) out[k] = p->coef[k * kNF + kFieldSlot[field]];
     return 0;
@@ -608,6 +844,7 @@ int torj_ray_entry(torj_plasma_t p, int n, const double *x0, const double *N0, d
                    int mode, double *xp, double *Np, double *s0, int *status) {
     if (!p) return fail("bad plasma handle");
     if (mode != 1 && mode != -1) return fail("mode must be +1 (X) or -1 (O)");
+    if (mirror_sync(p)) return -1;
     const double *coef = p->coef.data();
 #pragma omp parallel for schedule(dynamic, 16)
     for (int i = 0; i < n; i++) {

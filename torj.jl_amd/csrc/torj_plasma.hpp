@@ -122,6 +122,17 @@ static std::vector<double> uniform_range(double a, double b, int n) {
     return r;
 }
 
+// the 1-D half of make_2d_prof_spline (src/plasma.jl:16-22): a profile over psi resampled on
+// the uniform range, taken to its logarithm and prefiltered -> c1, n_prof + 2 coefficients
+static void prof1d_coefs(int n_prof, const double *psi_prof, const double *prof, std::vector<double> &c1) {
+    std::vector<double> pr = uniform_range(psi_prof[0], psi_prof[n_prof - 1], n_prof);
+    std::vector<double> p2(n_prof);
+    c1.assign((size_t)n_prof + 2, 0.0);
+    natcubic(n_prof, psi_prof, prof, n_prof, pr.data(), p2.data());
+    for (double &v : p2) v = std::log(v);
+    bspl1d_prefilter(n_prof, p2.data(), 1, c1.data(), 1);
+}
+
 struct torj_plasma_s {
     int device = 0;
     Grid g{};
@@ -186,15 +197,21 @@ struct torj_plasma_s {
     hipEvent_t ev_D = nullptr;
     hipEvent_t ev_Nin = nullptr, ev_Nout = nullptr;  // a NULL caller stream's fork / join
     hipEvent_t ev_U = nullptr;  // torj_plasma_update on a caller's stream: the handle's own stream waits for it
+    // torj_plasma_update_gpu / _profiles_gpu / _device: the coefficients are built on
+    // the device, and the host copies above go stale until a host reader asks for them (mirror_sync)
+    GrowBuf cbuild;             // staging of one build: the pivots, the two 1-D profile splines, Br, Bz, Bphi
+    double *d_psi = nullptr;    // the psi node map (nR x nZ), kept for profiles-only builds
+    bool d_psi_valid = false;   // d_psi holds the handle's psi_nodes
+    bool coef_stale = false;    // `coef` is older than d_coef
+    bool psi_stale = false;     // `psi_nodes` is older than d_psi
+    hipEvent_t ev_B = nullptr;  // the last build's end, which the downloads and the replicas' copies wait for
 };
 
 static const int kFieldSlot[6] = {F_PSI, F_LNNE, F_LNTE, F_BR, F_BZ, F_BPHI};
 
-static int plasma_finish(torj_plasma_s *p, int nR, int nZ, double R1, double Rn, double Z1,
-                         double Zn, const double *const fields[6], int device,
-                         torj_plasma_t *out) {
-    p->device = device;
-    Grid &g = p->g;
+// the grid of nR x nZ nodes over the box [R1, Rn] x [Z1, Zn]
+static Grid grid_box(int nR, int nZ, double R1, double Rn, double Z1, double Zn) {
+    Grid g{};
     g.nR = nR;
     g.nZ = nZ;
     g.R1 = R1;
@@ -205,6 +222,14 @@ static int plasma_finish(torj_plasma_s *p, int nR, int nZ, double R1, double Rn,
     g.hZ = (Zn - Z1) / (nZ - 1);
     g.invhR = 1.0 / g.hR;
     g.invhZ = 1.0 / g.hZ;
+    return g;
+}
+
+static int plasma_finish(torj_plasma_s *p, int nR, int nZ, double R1, double Rn, double Z1,
+                         double Zn, const double *const fields[6], int device,
+                         torj_plasma_t *out) {
+    p->device = device;
+    p->g = grid_box(nR, nZ, R1, Rn, Z1, Zn);
     const size_t nodes = (size_t)(nR + 2) * (nZ + 2);
     p->coef.assign(nodes * kNF, 0.0);
     for (int f = 0; f < 6; f++)
@@ -251,6 +276,26 @@ static int ensure_device(torj_plasma_s *p) {
 static int ensure_buf(torj_plasma_s *p, GrowBuf &b, size_t bytes) {
     std::lock_guard<std::mutex> lk(p->mu);
     return b.reserve(bytes);
+}
+
+// The host copies of what a device-side build (torj_plasma_update_gpu / _profiles_gpu / _device)
+// left on the device only: the host readers of `coef` and `psi_nodes` call this first.  It waits
+// for the build's event and downloads, once; a later host update replaces the copies instead.
+static int mirror_sync(torj_plasma_s *p) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->coef_stale && !p->psi_stale) return 0;
+    HIPCK(hipSetDevice(p->device));
+    HIPCK(hipEventSynchronize(p->ev_B));
+    if (p->coef_stale) {
+        HIPCK(hipMemcpy(p->coef.data(), p->d_coef, p->coef.size() * sizeof(double), hipMemcpyDeviceToHost));
+        p->coef_stale = false;
+    }
+    if (p->psi_stale) {
+        p->psi_nodes.resize((size_t)p->g.nR * p->g.nZ);
+        HIPCK(hipMemcpy(p->psi_nodes.data(), p->d_psi, p->psi_nodes.size() * sizeof(double), hipMemcpyDeviceToHost));
+        p->psi_stale = false;
+    }
+    return 0;
 }
 
 // a split-pipeline stream's priority: `dflt`, or the environment's value clamped

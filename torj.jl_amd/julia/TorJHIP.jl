@@ -133,6 +133,62 @@ function update!(h::GPUPlasma, p::TorJ.Plasma; stream::Ptr{Cvoid}=C_NULL)
     return h
 end
 
+"""update_gpu!(h, R, Z, psi_norm, psi_prof, ne, Te, Br, Bz, Bphi, eq_psi, eq_vol; stream=C_NULL) -- the
+raw maps of `GPUPlasma(R, Z, ...)` on the live handle `h` (torj_plasma_update_gpu): the six 2-D
+B-spline prefilters run on the GPU in `stream`'s order, the 1-D parts on the host.  The host arrays
+are consumed when the call returns; nothing synchronises."""
+function update_gpu!(h::GPUPlasma, R::Vector{Float64}, Z::Vector{Float64}, psi_norm::Matrix{Float64},
+                     psi_prof::Vector{Float64}, ne::Vector{Float64}, Te::Vector{Float64},
+                     Br::Matrix{Float64}, Bz::Matrix{Float64}, Bphi::Matrix{Float64},
+                     eq_psi::Vector{Float64}, eq_vol::Vector{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    (length(R), length(Z)) == (h.nR, h.nZ) ||
+        throw(ArgumentError("update_gpu! keeps the handle's grid size $((h.nR, h.nZ)), got $((length(R), length(Z)))"))
+    all(size(x) == (h.nR, h.nZ) for x in (psi_norm, Br, Bz, Bphi)) ||
+        throw(ArgumentError("update_gpu!: the 2-D maps must be $((h.nR, h.nZ))"))
+    check(ccall((:torj_plasma_update_gpu, libtorj), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h.h, R, Z, psi_norm, length(psi_prof), psi_prof, ne, Te, Br, Bz, Bphi,
+                length(eq_psi), eq_psi, eq_vol, stream))
+    h.psi_prof_max = maximum(psi_prof)
+    return h
+end
+
+"""update_profiles_gpu!(h, psi_prof, ne, Te; stream=C_NULL) -- new kinetic profiles on the
+equilibrium `h` last got as node data (torj_plasma_update_profiles_gpu): make_2d_prof_spline's
+node map and the two prefilters run on the GPU, from the psi nodes the handle keeps there."""
+function update_profiles_gpu!(h::GPUPlasma, psi_prof::Vector{Float64}, ne::Vector{Float64},
+                              Te::Vector{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    length(psi_prof) == length(ne) == length(Te) ||
+        throw(ArgumentError("psi_prof, ne and Te must have one length"))
+    check(ccall((:torj_plasma_update_profiles_gpu, libtorj), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h.h, length(psi_prof), psi_prof, ne, Te, stream))
+    h.psi_prof_max = maximum(psi_prof)
+    return h
+end
+
+"""update_device!(h, R, Z, d_psi_norm, psi_prof, ne, Te, d_Br, d_Bz, d_Bphi, eq_psi, eq_vol;
+stream=C_NULL) -- update_gpu! with the four 2-D maps as device pointers on the handle's device
+((nR, nZ) Float64, column-major, e.g. `pointer` of a ROCArray), read in `stream`'s order
+(torj_plasma_update_device): they must stay unchanged until the stream has passed the call."""
+function update_device!(h::GPUPlasma, R::Vector{Float64}, Z::Vector{Float64}, d_psi_norm::Ptr{Float64},
+                        psi_prof::Vector{Float64}, ne::Vector{Float64}, Te::Vector{Float64},
+                        d_Br::Ptr{Float64}, d_Bz::Ptr{Float64}, d_Bphi::Ptr{Float64},
+                        eq_psi::Vector{Float64}, eq_vol::Vector{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    (length(R), length(Z)) == (h.nR, h.nZ) ||
+        throw(ArgumentError("update_device! keeps the handle's grid size $((h.nR, h.nZ)), got $((length(R), length(Z)))"))
+    check(ccall((:torj_plasma_update_device, libtorj), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h.h, R, Z, d_psi_norm, length(psi_prof), psi_prof, ne, Te, d_Br, d_Bz, d_Bphi,
+                length(eq_psi), eq_psi, eq_vol, stream))
+    h.psi_prof_max = maximum(psi_prof)
+    return h
+end
+
 # one GPU copy per TorJ.Plasma object (make_ray / make_beam on TorJ's own type)
 const _gpu_cache = IdDict{Any,GPUPlasma}()
 const _gpu_lock = ReentrantLock()

@@ -74,6 +74,12 @@ _SIGS = {
                                                 C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int,
                                                 C.c_double, C.c_double, _dp, C.c_double, C.c_void_p]),
     "torj_plasma_update_profiles": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_void_p]),
+    # ... with the 2-D coefficients built on the device (_device: the four 2-D maps are device pointers)
+    "torj_plasma_update_gpu": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                         C.c_int, _dp, _dp, C.c_void_p]),
+    "torj_plasma_update_profiles_gpu": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_void_p]),
+    "torj_plasma_update_device": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, C.c_void_p]),
     "torj_plasma_get_cell_table": (C.c_int, [C.c_void_p, _dp]),
     "torj_eval_plasma": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_double, _dp]),
     "torj_dispersion": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp,

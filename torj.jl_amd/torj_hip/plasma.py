@@ -123,6 +123,60 @@ class Plasma:
         check(lib().torj_plasma_update_profiles(self._h, len(pp), dptr(pp), dptr(ne), dptr(te), stream))
         self.psi_prof_max = lib().torj_plasma_psi_prof_max(self._h)
 
+    # ---- ... with the 2-D coefficients built on the device (torj_plasma_update_gpu, _profiles_gpu, _device) ----
+    def update_gpu(self, R_coords, Z_coords, psi_norm_data, psi_prof, ne_prof, Te_prof, Br_data, Bz_data,
+                   Bphi_data, eqt1d_psi_norm, eqt1d_volume, stream=None):
+        """torj_plasma_update_gpu: update()'s arguments; the six 2-D prefilters run on the
+        GPU in `stream`'s order.  The handle's host copy of the coefficients goes stale:
+        coefs(), the host ray_entry, the host update_profiles and the creation of replicas
+        first wait for the build and download it (they synchronise)."""
+        R, Z = f64(R_coords), f64(Z_coords)
+        nR, nZ = len(self.R_coords), len(self.Z_coords)
+        if (len(R), len(Z)) != (nR, nZ):
+            raise ValueError(f"update_gpu keeps the grid size {(nR, nZ)}, got {(len(R), len(Z))}")
+
+        def m(a):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (nR, nZ):
+                raise ValueError(f"2-D map has shape {a.shape}, expected {(nR, nZ)}")
+            return np.ascontiguousarray(a.T)  # column-major (R fastest)
+
+        keep = [m(psi_norm_data), f64(psi_prof), f64(ne_prof), f64(Te_prof), m(Br_data),
+                m(Bz_data), m(Bphi_data), f64(eqt1d_psi_norm), f64(eqt1d_volume)]
+        check(lib().torj_plasma_update_gpu(self._h, dptr(R), dptr(Z), dptr(keep[0]), len(keep[1]),
+                                           dptr(keep[1]), dptr(keep[2]), dptr(keep[3]), dptr(keep[4]),
+                                           dptr(keep[5]), dptr(keep[6]), len(keep[7]), dptr(keep[7]),
+                                           dptr(keep[8]), stream))
+        self.R_coords, self.Z_coords = R, Z
+        self.psi_prof_max = lib().torj_plasma_psi_prof_max(self._h)
+
+    def update_profiles_gpu(self, psi_prof, ne_prof, Te_prof, stream=None):
+        """torj_plasma_update_profiles_gpu: update_profiles()'s arguments; the two 2-D
+        prefilters run on the GPU, from the psi nodes the handle keeps there."""
+        pp, ne, te = f64(psi_prof), f64(ne_prof), f64(Te_prof)
+        if not (len(pp) == len(ne) == len(te)):
+            raise ValueError("psi_prof, ne_prof and Te_prof must have one length")
+        check(lib().torj_plasma_update_profiles_gpu(self._h, len(pp), dptr(pp), dptr(ne), dptr(te), stream))
+        self.psi_prof_max = lib().torj_plasma_psi_prof_max(self._h)
+
+    def update_device(self, R_coords, Z_coords, psi_norm_data, psi_prof, ne_prof, Te_prof, Br_data, Bz_data,
+                      Bphi_data, eqt1d_psi_norm, eqt1d_volume, stream=None):
+        """torj_plasma_update_device: update_gpu() with the four 2-D maps as integer device
+        pointers (e.g. tensor.data_ptr()) on the handle's device: nR x nZ float64, R
+        fastest -- a contiguous (nZ, nR) tensor -- read in `stream`'s order, so they must
+        stay unchanged until the stream has passed the call."""
+        R, Z = f64(R_coords), f64(Z_coords)
+        nR, nZ = len(self.R_coords), len(self.Z_coords)
+        if (len(R), len(Z)) != (nR, nZ):
+            raise ValueError(f"update_device keeps the grid size {(nR, nZ)}, got {(len(R), len(Z))}")
+        keep = [f64(psi_prof), f64(ne_prof), f64(Te_prof), f64(eqt1d_psi_norm), f64(eqt1d_volume)]
+        maps = [int(v) for v in (psi_norm_data, Br_data, Bz_data, Bphi_data)]
+        check(lib().torj_plasma_update_device(self._h, dptr(R), dptr(Z), maps[0], len(keep[0]), dptr(keep[0]),
+                                              dptr(keep[1]), dptr(keep[2]), maps[1], maps[2], maps[3],
+                                              len(keep[3]), dptr(keep[3]), dptr(keep[4]), stream))
+        self.R_coords, self.Z_coords = R, Z
+        self.psi_prof_max = lib().torj_plasma_psi_prof_max(self._h)
+
     def cell_table(self) -> np.ndarray:
         """torj_plasma_get_cell_table: the per-cell power table on the device,
         (nZ - 1, nR - 1, 6, 4, 4): cell, field slot (Br, Bphi, Bz, ln ne, ln Te, psi),
