@@ -93,11 +93,12 @@ struct SplitArgs {
     double *stau, *spsi, *sPdep;  // the scan's carry
     int *sinfo;           // steps | status << 24: the scan's stop
     unsigned char *zflag;  // per ray, this block (ring slot): 1 = Albajar alpha provably +-0 at every
-                           // stage point the trajectory kernel stored (zero_box_flag); null: off
+                           // stage point the trajectory kernel stored (zero_box_flag), 2 = the same by
+                           // tiny_box_flag alone (tiny_alpha below), 0 = neither; null: off
     double zval;           // what a fully flagged alpha wave writes: 0, or NaN under the test hook
                            // TORJ_TEST_ZFLAG_NAN=1 (the flagged waves then stop their rays NAN)
     unsigned *gflag;       // per 64-ray group, this block (ring slot): 1 = every ray of the group carries
-                           // zflag 1.  Written once per wave by the trajectory kernel; the group's alpha
+                           // zflag 1, 2 = every ray carries 1 or 2, 0 = some ray carries 0.  Written once per wave by the trajectory kernel; the group's alpha
                            // waves end on it and the scan takes zval for the group's alphas (nothing is
                            // stored for them).  Null: off (TORJ_ALPHA_GFLAG=0, or zflag null)
     int k0, kb;           // block: steps [k0, k0 + kb)
@@ -114,6 +115,13 @@ struct SplitArgs {
     int zlatch;                 // the trajectory kernel's dead-box latch (traj_run; TORJ_ZBOX_LATCH=0 in the
                                 // environment turns it off).  In the struct's tail padding: the kernels'
                                 // arguments after a SplitArgs keep their offsets
+    double tiny_alpha;          // > 0: the trajectory kernel also flags a ray whose alpha is a zero over the
+                                // block by the tiny_alpha bound (tiny_box_flag; the Gauss-Legendre table's
+                                // tiny_alpha, m^-1); 0: zero_box_flag alone (split_tiny_alpha says when).
+                                // Such a ray's zflag byte is 2, and the word of a group that is wholly
+                                // flagged but not wholly by zero_box_flag is 2: every reader tests != 0
+    double tval;                // zval's twin for a byte / word 2: 0, or NaN under the test hook
+                                // TORJ_TEST_TFLAG_NAN (TORJ_TEST_ZFLAG_NAN keeps to the exact-zero proof)
 };
 
 // Word g of SplitArgs::gflag for the wave's own group (g wave-uniform), read

@@ -101,12 +101,17 @@ __global__ void __launch_bounds__(kAlphaBlock, TORJ_ALPHA_WAVES) k_alpha_pts(Tra
     // input loads below the stop test and the Te test, three latencies in a row)
     asm volatile("" ::"v"(ti), "v"(si), "v"(zf), "v"(X), "v"(Y), "v"(N2), "v"(Npar), "v"(lnTe));
     // without group words: a wave whose rays all carry the flag writes the zeros
-    // itself, as since round 6 (now behind the one batch, inputs included)
-    if (sp.gflag == nullptr && __all(zf != 0)) {
+    // itself, as since round 6 (now behind the one batch, inputs included).  Both
+    // ballots here, while zf is in hand: taken at the store, the second one kept zf
+    // alive across the head and cost the kernel two VGPRs (77 -> 79)
+    const bool per_ray = sp.gflag == nullptr;
+    const unsigned long long zb0 = per_ray ? __ballot(zf == 0) : 1ull, zb2 = per_ray ? __ballot(zf == 2) : 0ull;
+    if (zb0 == 0ull) {
 #if defined(TORJ_ALPHA_PROF) && defined(__HIP_DEVICE_COMPILE__)
         TORJ_APROF_WAVE(kAprofZ);
 #endif
-        sp.alpha[(size_t)js * a.n + i] = sp.zval;
+        // (all bytes 1: the exact-zero proof, sp.zval; some 2: the tiny_alpha proof, sp.tval)
+        sp.alpha[(size_t)js * a.n + i] = zb2 == 0ull ? sp.zval : sp.tval;
         if constexpr (COUNT) sp.awork[(size_t)js * a.n + i] = 0u;
         return;
     }

@@ -20,15 +20,16 @@ __device__ void cold_replay(const TraceArgs &a, const SplitArgs &sp, int i, doub
     const TileCell cg{a.cellp, nullptr, 0, 0, 0, 0};
     const TileCoef ng{a.coef, nullptr, 0, 0, 0, 0};
     ZBox zb;  // (unused: the replay stores no zero flags)
+    TBox tb;
     for (int s = 0; s < k; s++) {
         double xn[3], Nn[3], psi;
         double *o_run = ain_row(a, sp, 0, i);  // every step into row 0
         if (sp.traj_mode == kTrajCell)
-            cold_step<true, kTileNS, TileCell, true>(a, cg, sp, 0, i, x, N, xn, Nn, &psi, zb, false, o_run);
+            cold_step<true, kTileNS, TileCell, true>(a, cg, sp, 0, i, x, N, xn, Nn, &psi, zb, false, tb, false, o_run);
         else if (sp.traj_mode == kTrajTile)
-            cold_step<true, kTileNS, TileCoef, true>(a, ng, sp, 0, i, x, N, xn, Nn, &psi, zb, false, o_run);
+            cold_step<true, kTileNS, TileCoef, true>(a, ng, sp, 0, i, x, N, xn, Nn, &psi, zb, false, tb, false, o_run);
         else
-            cold_step<true, kNF, const double *, true>(a, a.coef, sp, 0, i, x, N, xn, Nn, &psi, zb, false, o_run);
+            cold_step<true, kNF, const double *, true>(a, a.coef, sp, 0, i, x, N, xn, Nn, &psi, zb, false, tb, false, o_run);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             x[c] = xn[c];
@@ -49,7 +50,11 @@ __device__ __forceinline__ void tau_scan_body(const TraceArgs &a, const SplitArg
     // the group's flag word (SplitArgs::gflag; the workgroup is the group, so a
     // scalar load, safe as in k_alpha_pts): a flagged group's alpha waves stored
     // nothing -- its alphas are sp.zval and its work words 0, taken from here
-    const bool gz = sp.gflag != nullptr && group_word(sp.gflag, (int)blockIdx.x) != 0u;
+    // (word 1: every ray flagged by the exact-zero proof, the alphas are sp.zval; word 2:
+    // some by the tiny_alpha proof alone, sp.tval -- both 0 outside the test hooks)
+    const unsigned gw = sp.gflag != nullptr ? group_word(sp.gflag, (int)blockIdx.x) : 0u;
+    const bool gz = gw != 0u;
+    const double gzv = gw == 1u ? sp.zval : sp.tval;
     if (i < a.n) {
         int steps = 0, st = ST_OK;
         double tau = 0.0, psi_a = 0.0, Pdep = 0.0;
@@ -86,7 +91,7 @@ __device__ __forceinline__ void tau_scan_body(const TraceArgs &a, const SplitArg
                 for (int v = 0; v < kScanBatch; v++) {
                     const size_t ov = (size_t)(min(sb + v, s_end - 1) - sp.k0) * 4 * a.n + i;
 #pragma unroll
-                    for (int q = 0; q < 4; q++) alb[v][q] = gz ? sp.zval : sp.alpha[ov + q * (size_t)a.n];
+                    for (int q = 0; q < 4; q++) alb[v][q] = gz ? gzv : sp.alpha[ov + q * (size_t)a.n];
                 }
 #pragma unroll
                 for (int v = 0; v < kScanBatch; v++) {

@@ -75,7 +75,8 @@ template <bool STORE, int NS = kNF, class CS = const double *, bool PSI = false>
 __device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
                                           const SplitArgs &sp, int j, int i, const double x[3],
                                           const double N[3], double xn[3], double Nn[3],
-                                          double *psi_x, ZBox &zb, bool zon, double *&o_run) {
+                                          double *psi_x, ZBox &zb, bool zon, TBox &tb, bool ton,
+                                          double *&o_run) {
     const double hds = 0.5 * a.ds, ds6 = a.ds / 6.0;
     double acc[6] = {0, 0, 0, 0, 0, 0}, xt[3], Nt[3], k[6];
 #pragma unroll
@@ -117,7 +118,21 @@ __device__ __forceinline__ bool cold_step(const TraceArgs &a, CS coef,
                 o = sp.ain + ((size_t)(j * 4 + st) * sp.nf) * a.n + i;
             }
             const double N2 = Nt[0] * Nt[0] + Nt[1] * Nt[1] + Nt[2] * Nt[2];
-            if (zon) zero_box_add(zb, p.lnTe, p.Y, Npar, N2);
+            if (zon) {
+                zero_box_add(zb, p.lnTe, p.Y, Npar, N2);
+                if (ton) {  // (ton implies zon; wave-uniform as well)
+                    // X = n_e Cx over again (the same bits as p.X) from an opaque copy of
+                    // n_e: a use of p.X's own product here, a block ahead of the dispersion's
+                    // arithmetic, kept the compiler from contracting 1 - X and X - 1 into
+                    // fmas there as it always had, and k_traj_cell's trajectories moved by
+                    // an ulp against every earlier build
+                    double ne = p.ne;
+#if defined(__HIP_DEVICE_COMPILE__)
+                    asm("" : "+v"(ne));
+#endif
+                    tiny_box_add(zb, tb, ne * a.k.Cx, N2);
+                }
+            }
             o[0] = p.X;
             o[(size_t)a.n] = p.Y;
             o[3 * (size_t)a.n] = Npar;
@@ -244,6 +259,15 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
     ZBox zb;
     bool zon = sp.zflag != nullptr;  // wave-uniform: the stages' branch around zero_box_add
     const bool zlatch = TORJ_ZBOX_LATCH && zon && sp.zlatch != 0;
+    // The block tiny box (torj_math.hpp TBox, tiny_box_flag): with SplitArgs::tiny_alpha
+    // > 0 a ray's flag is "zero_box_flag or tiny_box_flag" -- alpha an exact zero, or a
+    // zero because harmonic 3 is dismissed by the tiny_alpha bound, at every stage
+    // point of the block.  k_alpha_pts and the scan read the same byte and word.
+    TBox tb;
+    const bool ton = zon && sp.tiny_alpha > 0.0;
+    auto box_flag = [&]() -> bool {
+        return zero_box_flag(zb) || (ton && tiny_box_flag(zb, tb, a.omega, a.mode, sp.tiny_alpha));
+    };
     int trips = 0;  // of the wave's step loop (uniform, unlike s)
 #if defined(__HIP_DEVICE_COMPILE__) && TORJ_TRAJ_PREWAIT
     // every load before the step loop complete here (s_waitcnt vmcnt(0)): the
@@ -255,7 +279,7 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
     double *o_run = ain_row(a, sp, (s_first - sp.k0) * 4, i);  // cold_step's store pointer (the cell kernel)
     for (int s = s_first; s < s_end; s++) {
         double xn[3], Nn[3], psi_x;
-        const bool bad = cold_step<true, NS, CS, true>(a, coef, sp, s - sp.k0, i, x, N, xn, Nn, &psi_x, zb, zon, o_run);
+        const bool bad = cold_step<true, NS, CS, true>(a, coef, sp, s - sp.k0, i, x, N, xn, Nn, &psi_x, zb, zon, tb, ton, o_run);
         if (pending) {
             pending = false;
             if (step_end(s - 1, psi_x)) {
@@ -292,7 +316,9 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
                 cb[(3 + c) * (size_t)a.n] = N[c];
             }
         }
-        // The dead-box latch.  zero_box_flag is monotone: a further point only
+        // The dead-box latch, over "zero_box_flag or tiny_box_flag" (box_flag; the
+        // second is monotone for the same reason, tests/test_tiny_box_host.py).
+        // zero_box_flag is monotone: a further point only
         // raises lte, yhi, np2 and chk's NaN and lowers ylo and perp, and each of
         // its conditions only gets harder that way, so a box whose flag is false
         // stays false to the end of the block (swept on the CPU by
@@ -305,7 +331,7 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
         if (zlatch && zon) {
             trips++;
             if (trips == kZLatchTrip0 || trips == kZLatchTrip1) {
-                if (!__any(zero_box_flag(zb))) {
+                if (!__any(box_flag())) {
                     zero_box_kill(zb);
                     zon = false;
                 }
@@ -322,14 +348,18 @@ __device__ __forceinline__ void traj_run(const TraceArgs &a, const SplitArgs &sp
     }
     sp.tinfo[i] = make_info(steps, st);
     if (sp.zflag != nullptr) {
-        const bool zf = zero_box_flag(zb);
-        sp.zflag[i] = zf ? 1 : 0;
+        // byte 1: the exact-zero proof; 2: the tiny_alpha proof alone (SplitArgs::tiny_alpha)
+        const bool zf0 = zero_box_flag(zb);
+        const bool zf = zf0 || box_flag();
+        sp.zflag[i] = zf0 ? 1 : (zf ? 2 : 0);
         // the group's word (SplitArgs::gflag): the lanes here are the wave's rays
         // with steps in this block, reconverged behind the step loop; a lane that
         // left in traj_body carries flag 1 by definition, so the `all` over these
         // is the group's.  Every one of them stores the same word to the same
         // address: the wave's one store, whichever lanes are left
-        if (sp.gflag != nullptr) sp.gflag[i >> 6] = __all(zf) ? 1u : 0u;
+        // (word 1 only when every one of them has the exact-zero proof: a ray that
+        // left earlier counts as such, as its byte says)
+        if (sp.gflag != nullptr) sp.gflag[i >> 6] = __all(zf) ? (__all(zf0) ? 1u : 2u) : 0u;
     }
 }
 

@@ -551,7 +551,9 @@ static int trace_device_one(torj_plasma_t p, const torj_trace_cfg *cfg, const Ra
     DepoStream dstr{};  // the split pipeline's streamed deposition (split_trace)
     switch (pl.path) {
     case kPathSplit:
-        if (split_trace(p, a, pl.DM, pl.tr, s, pl.fit ? &fa : nullptr, &dstr, g_gl_host.negl_skip != 0)) return -1;
+        if (split_trace(p, a, pl.DM, pl.tr, s, pl.fit ? &fa : nullptr, &dstr, g_gl_host.negl_skip != 0,
+                        g_gl_host.tiny_alpha))
+            return -1;
         break;
     case kPathQueue:
         if (launch_queue(p, a, pl, s)) return -1;

@@ -1864,6 +1864,147 @@ TORJ_HD bool zero_box_flag(const ZBox &b) {
 // flag is false from here on, whatever is added.
 TORJ_HD void zero_box_kill(ZBox &b) { b.chk = NAN; }
 
+// The block tiny box: beside a ray's ZBox, the three further extremes from which
+// tiny_box_flag proves that abs_albajar_fast_body, with negl_skip on and this
+// tiny_alpha, returns +-0 (never NaN) at every stage point of the block although
+// harmonic 3 is no exact zero there: it is dismissed by the tiny_alpha bound.
+// X joins the zero box's chk word (a NaN or infinite X refuses both flags from
+// then on; v_min_f64 / v_max_f64 would pass over a NaN), so zero_box_kill
+// silences this flag too.
+// max |N|^2 is kept in single precision, rounded up (it enters only the bounds on
+// xi and N_eff, where 2^-22 is nothing): with a third double, k_traj_cell<2, true>
+// held 177 VGPRs against its budget of 176 (tests/test_traj_resources.py).
+struct TBox {
+    double xlo = INFINITY, xhi = -INFINITY;  // min X, max X
+    float n2 = -INFINITY;                    // max |N|^2, from above
+};
+TORJ_HD float tb_max(float a, float b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return fmaxf(a, b);
+#endif
+}
+TORJ_HD void tiny_box_add(ZBox &b, TBox &t, double X, double N2) {
+    t.xlo = zb_min(t.xlo, X);
+    t.xhi = zb_max(t.xhi, X);
+    // (float)N2 is within 2^-24 of N2 >= 0 (an overflow is +inf, which the flag refuses)
+    t.n2 = tb_max(t.n2, (float)N2 * (1.0f + 0x1p-22f));
+    b.chk = fma(X, 0.0, b.chk);
+}
+// True only when, at every point (X, Y, |N|, N_par, Te) the two boxes cover,
+// the body's harmonic 2 is absent or an exact zero (zero_box_flag's two tests,
+// unchanged: "harmonic 2 below tiny_alpha" is not taken) and its harmonic 3, if
+// present, ends on one of albajar_harmonic's zeros or on the tiny_alpha skip --
+// h3_fast_negligible's B < hmax, or B0 E_max < hmax in albajar_harmonic<3> itself
+// (GLTable::h3_fast off; U >= 2 B0 and 2^(ceil(y_ub) + 1) >= E_max in both forms
+// of the node exponent, as h3_fast_bound states) -- so that albajar_finish
+// multiplies a zero by finite factors.  False whenever tiny_alpha <= 0.
+//
+// Intervals over the box, [lo, hi], of what albajar_prologue computes; every
+// step's interval holds the computed value, not only the exact one, by the
+// slack written beside it (the prologue's operations are good to a few ulp of
+// operands of order 1 once the guards below hold), and every refusal and the
+// final inequality only get harder as the box grows -- each bound is monotone
+// in the extremes and rounding is monotone -- so the flag, once false, stays
+// false (the dead-box latch of traj_run).
+//   c2 = cos^2 in [0, np2 / (np2 + perp)], s2 = 1 - c2;
+//   rho^2 = Y^2 s2^2 + 4 (1 - X)^2 c2, term by term;
+//   D = 2 (1 - X) - Y^2 s2 - mode Y rho > 1e-3 (the dispersion's denominator:
+//     away from the cut-off and resonance of the mode), f = 2 (1 - X) / D;
+//   Nt^2 = 1 - X f in (1e-6, 1] (outside, the prologue's own early returns
+//     give the zero, but nothing is proved about the points beside them);
+//   g = 1 - (1 - Y^2) f, |g| at the corners;
+//   den = (1 - X) - Nt^2 s2 of one sign and 1e-9 away from 0 (den -> 0 as
+//     X -> 0: hence min X), unless the whole box takes the quasi-perpendicular
+//     branch (c2 < 1e-5), which has no den;
+//   ta >= 1 gives a_sq + b_sq >= s2: ea^2 <= 1 / (Nt sqrt(s2)), and the
+//     quasi-perpendicular sqrt(1 / Nt) is below that; |e1| <= |g| / Y ea;
+//     |e3| <= Nt^2 sqrt(s2 c2) / |den| |e1|, or Nt^-1/2;
+//   s = 1 / sqrt(1 - N_par^2), xi = N_perp s <= |N| s, |N_eff| <= |N| |N_par| s^2,
+//   S <= |e1| + |N_eff| |e3| + |ea| + |e3| (1 + xi s): h3_fast_bound's S;
+//   U <= mu r^3 xi^4 S^2 (45.5625 + 7.59375 xi^2) with r = 3 Y s and mu <= mu(20
+//     eV): colder points return 0 before anything else;
+//   y_ub <= -mu_lo log2(e) (G - 1), G = 3 Y_lo / (1 + |N_par|_hi) > 1 (harmonic 3
+//     present and below its resonance everywhere), mu_lo from the box's largest Te;
+//   tiny_harmonic's hmax >= tiny_alpha / 2 / (F sqrt(mu / 2 pi)), F <= 2 pi^2 s X
+//     omega / c mu / (2 pi) (its inv_m0 omega_bar is s).
+// The flag: U 2^(ceil(y_ub) + 1) 2^20 < hmax, the 2^20 against the roundings of
+// both sides and of the body's own U and hmax (relative 1e-6 at the worst: den
+// at its guard).  On the headline fan the left side is below 2^-230 of the right
+// wherever the flag fires (tests/test_tiny_box_host.py).
+TORJ_HD bool tiny_box_flag(const ZBox &b, const TBox &t, double omega, int mode, double tiny_alpha) {
+    if (!(tiny_alpha > 0.0 && tiny_alpha < 1.0)) return false;
+    if (!(b.chk == 0.0)) return false;
+    if (!(omega > 1.0 && omega < 1e20)) return false;
+    constexpr double kNp2Max = 1.0 - 1e-6;
+    // zero_box_flag's ranges, narrowed: Y < 1, 20 eV .. e^40 eV, X inside (1e-12, 1)
+    if (!(b.ylo > 1e-3 && b.yhi < 1.0 && b.perp > 1e-12 && b.np2 < kNp2Max && b.np2 >= 0.0 && b.lte < 40.0 &&
+          b.lte > -700.0 && t.xlo > 1e-12 && t.xhi < 1.0 && t.n2 < 1e6))
+        return false;
+    constexpr double kMuTe = kMe * kC * kC / kE;  // mu Te (albajar_pre)
+    const double npm = sqrt(b.np2), sq = sqrt(1.0 - b.np2);
+    {  // harmonic 2 absent or an exact zero over the box: zero_box_flag's tests
+        const double delta = 760.0 * (1.0 + 1e-9) * exp(b.lte) * (1.0 / kMuTe);
+        const bool absent = 2.0 * b.yhi * (1.0 + 1e-9) < sq * (1.0 - 1e-9);
+        const bool zero = 2.0 * b.ylo > (1.0 + delta) * (1.0 + npm) * (1.0 + 1e-9);
+        if (!(absent || zero)) return false;
+    }
+    const double s_hi = 1.0 / sq, s2h = s_hi * s_hi;
+    const double G = 3.0 * b.ylo / (1.0 + npm);
+    // y_ub's own slack (h3_fast_bound: 1e-13 on 1 and on 1 - |N_par|, the latter times r s <= 3 Y s^2)
+    const double gm1 = (G - 1.0) - 1e-12 - 3e-12 * b.yhi * s2h;
+    if (!(gm1 > 1e-9)) return false;  // (harmonic 3 absent everywhere is zero_box_flag's case)
+    // the polarisation vector's intervals
+    const double c2h = fmin(b.np2 / (b.np2 + b.perp) * (1.0 + 1e-9), 1.0);
+    const double s2l = 1.0 - c2h - 1e-12;
+    if (!(s2l > 1e-6)) return false;
+    const double oxl = 1.0 - t.xhi, oxh = 1.0 - t.xlo;  // (exact in the body too: Sterbenz or one rounding, monotone)
+    const double yl2 = b.ylo * b.ylo, yh2 = b.yhi * b.yhi;
+    const double rhol = b.ylo * s2l * (1.0 - 1e-12);
+    const double rhoh = sqrt(yh2 + 4.0 * oxh * oxh * c2h) * (1.0 + 1e-12);
+    const double m = (double)mode, tl = -m * (b.ylo * rhol), th = -m * (b.yhi * rhoh);
+    const double Dl = 2.0 * oxl - yh2 + fmin(tl, th) - 1e-12;
+    const double Dh = 2.0 * oxh - yl2 * s2l + fmax(tl, th) + 1e-12;
+    if (!(Dl > 1e-3 && Dh < 1e3)) return false;
+    const double fl = 2.0 * oxl / Dh * (1.0 - 1e-10), fh = 2.0 * oxh / Dl * (1.0 + 1e-10);
+    const double nt2l = 1.0 - t.xhi * fh - 1e-12, nt2h = fmin(1.0 - t.xlo * fl + 1e-12, 1.0 + 1e-12);
+    if (!(nt2l > 1e-6)) return false;
+    const double g1 = 1.0 - (1.0 - yl2) * fh, g2 = 1.0 - (1.0 - yh2) * fl;
+    const double gh = fmax(fabs(g1), fabs(g2)) + 1e-12;
+    const double inv_ntl = 1.0 / sqrt(nt2l);  // >= 1 / Nt
+    const double ea_h = sqrt(inv_ntl / sqrt(s2l)) * (1.0 + 1e-9);
+    const double e1_h = gh / b.ylo * ea_h * (1.0 + 1e-9);
+    double e3_h = sqrt(inv_ntl) * (1.0 + 1e-9);
+    if (!(c2h < 1e-5 * (1.0 - 1e-6))) {  // some point may take the oblique branch
+        const double dl = oxl - nt2h - 1e-12, dh = oxh - nt2l * s2l + 1e-12;  // s2 <= 1
+        const double ad = dl > 0.0 ? dl : -dh;  // |den| from below when den keeps one sign
+        if (!(ad > 1e-9)) return false;
+        e3_h = fmax(e3_h, nt2h * sqrt(c2h) / ad * e1_h * (1.0 + 1e-6));
+    }
+    const double nh = sqrt((double)t.n2), xi_h = nh * s_hi * (1.0 + 1e-9);
+    // x_3 <= 3 xi: inside the range in which the Bessel series of the exact leg
+    // (tiny_alpha 0) is itself accurate, so that the promise |alpha| <= 2 tiny_alpha
+    // holds against what that leg computes; physical rays have x_3 < 3
+    if (!(xi_h <= 4.0)) return false;
+    const double S_h = (e1_h + nh * npm * s2h * e3_h + ea_h + e3_h * (1.0 + xi_h * s_hi)) * (1.0 + 1e-6);
+    const double mu_h = kMuTe / 20.0 * (1.0 + 1e-9);
+    const double r_h = 3.0 * b.yhi * s_hi * (1.0 + 1e-9);
+    const double xi2 = xi_h * xi_h;
+    const double U_h = mu_h * (r_h * r_h * r_h) * (xi2 * xi2) * (S_h * S_h) * (45.5625 + 7.59375 * xi2);
+    // tiny_harmonic from below
+    const double m_h = mu_h * (1.0 / (2.0 * kPi));
+    const double F_h = (2.0 * kPi * kPi) * s_hi * t.xhi * omega * (1.0 / kC) * m_h * (1.0 + 1e-9);
+    const double hmax_l = 0.5 * tiny_alpha / (F_h * sqrt(m_h)) * (1.0 - 1e-9);
+    if (!(U_h < 1e250 && hmax_l > 1e-250 && F_h < 1e250)) return false;
+    const double mu_l = kMuTe * exp(-b.lte) * (1.0 - 1e-9);
+    const double y_ub = -(mu_l * 1.4426950408889634074) * gm1 * (1.0 - 1e-9);
+    const double E = ldexp(1.0, (int)fmax(fmin(ceil(y_ub) + 1.0, 2000.0), -1000.0));
+    return U_h * E * 0x1p20 < hmax_l;
+}
+
 // the fused trace kernels' call (out of line there, see TORJ_ALB_ATTR); kernels
 // with nothing else to hold (the split path's alpha kernel) inline the body
 template <int LPR = 1>

@@ -182,6 +182,17 @@ static void split_plan_sizes(SplitPlan &pl, int sched_mode, int sched_waves, siz
     pl.defer_lrm = std::min(3, std::max(0, env_int("TORJ_WARM_DEFER_LRM", 3)));
 }
 
+// SplitArgs::tiny_alpha of a launch: the Gauss-Legendre table's tiny_alpha where the
+// trajectory kernel may flag a block by the tiny_alpha bound (tiny_box_flag), else 0.
+// Off without the block flags (which need the early settle, negl_skip), in the exact
+// leg (tiny_alpha 0), with TORJ_ZBOX_TINY=0 (read per call), and in a counted launch:
+// like the h3_fast shortcut, it would move the work counters (a flagged wave counts
+// nothing), and bench.py's FLOP model is built on them.
+static double split_tiny_alpha(const SplitPlan &pl, const TraceArgs &a, double tiny_alpha) {
+    if (!pl.zflag_on || a.counters || !(tiny_alpha > 0.0)) return 0.0;
+    return env_int("TORJ_ZBOX_TINY", 1) != 0 ? tiny_alpha : 0.0;
+}
+
 // the ring slots and single arrays carved out of the handle's split workspace
 struct SplitRing {
     static constexpr int R = SplitPlan::R;
@@ -244,7 +255,7 @@ static int split_plan(SplitPlan &pl, const torj_plasma_s *p, const TraceArgs &a,
 // trajectory runs up to kRing blocks ahead of the alpha; forked from and
 // joined back into `s`.
 static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream_t s, const FitArgs *fa,
-                       DepoStream *dso, bool negl_skip) {
+                       DepoStream *dso, bool negl_skip, double tiny_alpha) {
     SplitPlan pl;
     if (split_plan(pl, p, a, DM, fa && dso, negl_skip)) return -1;
     constexpr int R = SplitPlan::R;
@@ -262,6 +273,19 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
     sp.zval = 0.0;
     sp.defer_lrm = pl.defer_lrm;
     sp.zlatch = pl.zlatch;
+    sp.tiny_alpha = split_tiny_alpha(pl, a, tiny_alpha);
+    sp.tval = 0.0;
+    // test hook only (tests/test_gpu_tiny_flags.py): TORJ_TEST_TFLAG_NAN=s -- TORJ_TEST_ZFLAG_NAN's
+    // twin for the groups flagged by the tiny_alpha proof (word 2): their alphas are NaN in
+    // the blocks that start at step s or later.  Two hooks, so that a test can tell which
+    // proof flagged a group, and the older hook's tests see the groups they always saw
+    const int tflag_nan_from = env_has("TORJ_TEST_TFLAG_NAN") ? std::max(0, env_int("TORJ_TEST_TFLAG_NAN", 0)) : -1;
+    if (tflag_nan_from >= 0) {
+        static std::atomic<bool> warned{false};
+        if (!warned.exchange(true))
+            fprintf(stderr, "libtorj_hip: TORJ_TEST_TFLAG_NAN is set -- a TEST HOOK: alpha waves fully "
+                            "flagged by the tiny_alpha proof write NaN\n");
+    }
 
     const bool serial = pl.serial, dstream = pl.dstream;
     // the scan on a third stream (TORJ_SPLIT_SCAN=0: behind the alpha kernel on
@@ -321,6 +345,7 @@ static int split_trace(torj_plasma_s *p, TraceArgs a, int DM, bool tr, hipStream
         sp.zflag = rg.zflags[r];
         sp.gflag = rg.gflags[r];  // null when the group words are off
         sp.zval = (pl.zflag_nan_from >= 0 && sp.k0 >= pl.zflag_nan_from) ? NAN : 0.0;
+        sp.tval = (tflag_nan_from >= 0 && sp.k0 >= tflag_nan_from) ? NAN : 0.0;
         sp.alpha = rg.alphas[r];
         sp.awork = pl.b_awork ? rg.aworks[r] : nullptr;  // work words only for a counted launch
         // this ring slot's previous readers (alpha and scan of block b - R) are done
