@@ -47,7 +47,8 @@ extern "C" {
                                torj_plasma_update_from_coefs, torj_plasma_update_profiles,
                                torj_plasma_get_cell_table;
                                still 8 (three more symbols, nothing changed): torj_plasma_update_gpu,
-                               torj_plasma_update_profiles_gpu, torj_plasma_update_device */
+                               torj_plasma_update_profiles_gpu, torj_plasma_update_device;
+                               still 8 (one more symbol, nothing changed): torj_make_beams */
 
 /* per-ray status codes (replace the reference's @assert / unhandled returns) */
 enum torj_status {
@@ -466,6 +467,85 @@ int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_
                                      const double *omega, const int *mode, const double *x0,
                                      const double *N0, double *x_plasma, double *N_plasma,
                                      double *s0, int *status);
+
+/* ---- make_beams: many launchers in one call; failed entries reported ---------
+ * make_beam (src/solve.jl:209-242) for n_beams launchers at once, the five-call
+ * sequence torj_launch_peripheral_rays per launcher, torj_ray_entry_beams*_gpu,
+ * torj_trace_beams*, torj_shell_volumes as one entry point.  Unlike the
+ * reference's @assert (src/solve.jl:138,141) a ray that fails the ray entry does
+ * not end the call: it is reported, per beam, and the rays that entered are
+ * traced -- a candidate angle of a steering or density scan whose beam grazes or
+ * misses the plasma is an outcome, not an error.
+ *
+ * Launch (host): per launcher N0 = torj_pol_tor_angles_2_vector(pol, tor),
+ * x0 = (r cos phi, r sin phi, z), omega = 2 pi f, and the rays of
+ * torj_launch_peripheral_rays(x0, N0, spot_size, inverse_curvature_radius, f,
+ * N_rings, min_azimuthal_points, normalize_weight_sum = 1); the launchers' ray
+ * counts may differ.  Entry (GPU) of all n rays, torj_ray_entry_beams[_plasmas]_device.
+ * The rays that entered are closed up, launched order kept within each beam, and
+ * traced by one torj_trace_beams[_plasmas]_device launch with that call's plans
+ * and lanes per ray on the kept counts; their weights are NOT renormalised, so
+ * deposited_power is the share of the beam's power that coupled and was absorbed
+ * and w_ok says how much coupled.  A beam none of whose rays entered is an empty
+ * beam: its row is 0.
+ *
+ * Plasmas: n_plasmas == 0 and plasmas == NULL send every beam through p; else
+ * beam b goes through plasmas[launchers[b].plasma] under the rules of
+ * torj_trace_beams_plasmas (p the launching handle).  cfg: omega and mode are
+ * ignored (the launchers give them); the rest is torj_trace_beams', with its
+ * refusals.  psi_dP_dV: n_psi >= 2 shell boundaries, strictly increasing.
+ * Outputs (host, each may be NULL): dP_dV, n_beams x n_psi, row b = row b of
+ * torj_trace_beams' dP_shell over the shell volumes of beam b's plasma
+ * (torj_shell_volumes), its last entry 0; res, n_beams; ray_off, n_beams + 1, the
+ * launched offsets: beam b owns rays ray_off[b] .. ray_off[b + 1] - 1 of every
+ * per-ray array; rays, the per-ray arrays over all n = ray_off[n_beams] launched
+ * rays, laid out as the single calls lay them out.  A ray that failed entry has
+ * status = its entry status (TORJ_RAY_REFLECTED or TORJ_RAY_ENTRY_FAIL), steps 0,
+ * P_dep 0 and NaN in state and in its traj columns.
+ * With dP_dV, res and rays all NULL and ray_off given the call only counts the
+ * rays: the two-call pattern of torj_launch_peripheral_rays.  Then only
+ * launchers, n_beams, N_rings and min_azimuthal_points are read; of each launcher
+ * f and mode are checked as in the full call, plasma is not.
+ *
+ * Host pointers, synchronous, checked (torj_trace_check runs inside).  Every
+ * argument is checked before any device work; the message starts with
+ * "torj_make_beams:" and names the argument, and torj_trace_beams' argument
+ * refusals follow, also before any device work.  Its workspace-budget refusal
+ * (TORJ_WS_GB) alone needs the device and the kept counts: it comes after the
+ * entry has run.  The per-ray device arrays live in a grow-only buffer of the
+ * handle p, released with the handle: nothing per ray is allocated per call once
+ * it has grown.  It holds every per-ray array twice, launched and kept, both at
+ * the launched count (sized once, before the entry): 41 + 10 n_save doubles and
+ * 7 ints per launched ray, n_save = n_steps / traj_stride samples when rays->traj
+ * is given, else 0 -- for 1 104 rays and 2 000 samples 2 x 88 MB. */
+typedef struct {
+    double r, phi, z;                              /* make_beam's launch point (src/solve.jl:212-215) */
+    double steering_angle_tor, steering_angle_pol;
+    double spot_size, inverse_curvature_radius;
+    double f;                                      /* Hz */
+    int mode;                                      /* +1 X, -1 O */
+    int plasma;                                    /* index into plasmas[]; unused when n_plasmas == 0 */
+} torj_launcher;
+
+typedef struct {
+    int n_rays, n_ok;                 /* rays launched; rays that passed entry */
+    int first_bad_ray, first_bad_status; /* within the beam; -1, 0 when n_ok == n_rays */
+    double w_ok;                      /* sum of the launched weights of the rays that entered */
+    double deposited_power;           /* make_beam's (dP_shell[n_psi] of the beam's row) */
+} torj_beam_result;
+
+typedef struct {   /* all host arrays, each may be NULL; n = sum of n_rays, launched order */
+    double *pos, *dir, *weights;      /* 3 x n, 3 x n, n: launch_peripheral_rays' outputs */
+    double *x_plasma, *N_plasma, *s0; /* ray entry's */
+    int *entry_status;
+    double *state; int *status, *steps; double *P_dep; double *traj;  /* torj_trace_beams' */
+} torj_beams_rays;
+
+int torj_make_beams(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                    int n_beams, const torj_launcher *launchers, int N_rings,
+                    int min_azimuthal_points, const torj_trace_cfg *cfg, int n_psi,
+                    const double *psi_dP_dV, double *dP_dV, torj_beam_result *res,
+                    int *ray_off, const torj_beams_rays *rays);
 
 /* make_beam's fan-out and reduce across the GPUs of this process
  * (src/solve.jl:209-240: one task per ray, then sum_i w_i dP_dV_i and

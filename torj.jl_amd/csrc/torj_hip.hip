@@ -725,6 +725,7 @@ int torj_plasma_destroy(torj_plasma_t p) {
     for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
     if (p->ws.d) (void)hipFree(p->ws.d);
     if (p->beams.d) (void)hipFree(p->beams.d);
+    if (p->mk.d) (void)hipFree(p->mk.d);
     if (p->split.d) (void)hipFree(p->split.d);
     if (p->batch.d) (void)hipFree(p->batch.d);
     for (int q = 0; q < torj_plasma_s::kRing; q++) {
@@ -759,11 +760,16 @@ int torj_plasma_volume(torj_plasma_t p, int n, const double *psi, double *vol) {
     return 0;
 }
 
-int torj_shell_volumes(torj_plasma_t p, int n_psi, const double *g, double *dV) {
-    if (!p) return fail("bad plasma handle");
+// (torj_shell_volumes, and torj_make_beams' division of its dP_shell rows)
+static void shell_volumes(const torj_plasma_s *p, int n_psi, const double *g, double *dV) {
     for (int j = 0; j + 1 < n_psi; j++)
         dV[j] = bspl1d_eval(p->vol_coef, p->n_vol, p->v1, p->vn, g[j + 1]) -
                 bspl1d_eval(p->vol_coef, p->n_vol, p->v1, p->vn, g[j]);
+}
+
+int torj_shell_volumes(torj_plasma_t p, int n_psi, const double *g, double *dV) {
+    if (!p) return fail("bad plasma handle");
+    shell_volumes(p, n_psi, g, dV);
     return 0;
 }
 
@@ -1105,6 +1111,143 @@ static int entry_beams_host(torj_plasma_t p, const PlasmaSel *ps, const BeamTabl
     return entry_staged(p, h, [&](const EntryIO &d, hipStream_t s) { return entry_beams_device(p, ps, bt, d, s); });
 }
 
+// ---- make_beams as one call (torj_make_beams): the launchers' fans on the host, the ray entry
+// of all rays on the GPU, the rays that entered closed up (beams_compact, k_rays_gather), one
+// multi-beam trace of those, its outputs back in launched order (k_rays_scatter) ----
+struct BeamFans {  // every launcher's rays, concatenated in launcher order, and the beams' tables
+    std::vector<int> off, mode, beam_pl;  // n_beams + 1, n_beams, n_beams
+    std::vector<double> omega;            // n_beams
+    std::vector<double> pos, dir, w;      // 3 x n, 3 x n, n, component-major over all n rays
+};
+
+// make_beam's launch per launcher (src/solve.jl:211-216) by the functions the single calls use;
+// count_only stops at the offsets
+static int make_beams_fans(BeamFans &F, int n_beams, const torj_launcher *la, int N_rings, int min_az,
+                           bool count_only) {
+    F = BeamFans{};
+    F.off.assign(1, 0);
+    std::vector<double> x0(3 * (size_t)n_beams), N0(3 * (size_t)n_beams);
+    for (int b = 0; b < n_beams; b++) {
+        const torj_launcher &l = la[b];
+        torj_pol_tor_angles_2_vector(l.steering_angle_pol, l.steering_angle_tor, &N0[3 * b]);
+        x0[3 * b] = l.r * std::cos(l.phi), x0[3 * b + 1] = l.r * std::sin(l.phi), x0[3 * b + 2] = l.z;
+        int nb = 0;
+        if (torj_launch_peripheral_rays(&x0[3 * b], &N0[3 * b], l.spot_size, l.inverse_curvature_radius, l.f, N_rings,
+                                        min_az, 1, &nb, nullptr, nullptr, nullptr))
+            return -1;
+        if ((long long)F.off[b] + nb > 0x7fffffffll / 8)
+            return fail("torj_make_beams: launchers 0..%d launch more than %d rays", b, 0x7fffffff / 8);
+        F.off.push_back(F.off[b] + nb);
+        F.omega.push_back(2.0 * kPi * l.f);
+        F.mode.push_back(l.mode);
+        F.beam_pl.push_back(l.plasma);
+    }
+    if (count_only) return 0;
+    const size_t n = (size_t)F.off[n_beams];
+    F.pos.resize(3 * n), F.dir.resize(3 * n), F.w.resize(n);
+    std::vector<double> pos, dir;
+    for (int b = 0; b < n_beams; b++) {
+        const torj_launcher &l = la[b];
+        const size_t lo = (size_t)F.off[b], nb = (size_t)F.off[b + 1] - lo;
+        pos.resize(3 * nb), dir.resize(3 * nb);
+        if (torj_launch_peripheral_rays(&x0[3 * b], &N0[3 * b], l.spot_size, l.inverse_curvature_radius, l.f, N_rings,
+                                        min_az, 1, nullptr, pos.data(), dir.data(), F.w.data() + lo))
+            return -1;
+        for (int c = 0; c < 3; c++) {
+            std::copy(pos.begin() + c * nb, pos.begin() + (c + 1) * nb, F.pos.begin() + c * n + lo);
+            std::copy(dir.begin() + c * nb, dir.begin() + (c + 1) * nb, F.dir.begin() + c * n + lo);
+        }
+    }
+    return 0;
+}
+
+// the device part, enqueued: entry, compaction, trace, and every output the caller asked for.
+// est: the n entry statuses; dP: n_beams rows of n_psi + 1 (dP_shell as torj_trace_beams gives
+// it); idx: the gather index and its inverse, the caller's because the stream copies from it
+static int make_beams_enqueue(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, const BeamFans &F,
+                              int n_psi, const double *grid, const torj_beams_rays &out, std::vector<int> &est,
+                              BeamsCompact &bc, std::vector<double> &dP, std::vector<int> &idx) {
+    const int B = (int)F.omega.size(), n = F.off[B];
+    const size_t N = (size_t)n, rows = dP_rows(B, n_psi);
+    const int n_save = out.traj && cfg->traj_stride > 0 ? cfg->n_steps / cfg->traj_stride : 0;
+    est.assign(N, 0);  // (n >= 2 n_beams: every ring of a fan has a ray)
+    dP.assign(rows, 0.0);
+    if (ensure_devices(p, ps)) return -1;
+    hipStream_t s = p->stream;
+    // one grow-only buffer of the handle holds every array of the call: the kept rays' arrays
+    // at the launched size too, so that it is sized before the entry has run
+    size_t bytes = 0;
+    auto take = [&](size_t b) {
+        const size_t at = bytes;
+        bytes += (b + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t D = sizeof(double), I = sizeof(int), T = (size_t)n_save * 5 * N * D;
+    const size_t o_pos = take(3 * N * D), o_dir = take(3 * N * D), o_w = take(N * D), o_xp = take(3 * N * D),
+                 o_Np = take(3 * N * D), o_s0 = take(N * D), o_state = take(7 * N * D), o_Pdep = take(N * D),
+                 o_traj = take(T), o_pos_c = take(3 * N * D), o_w_c = take(N * D), o_xp_c = take(3 * N * D),
+                 o_Np_c = take(3 * N * D), o_s0_c = take(N * D), o_state_c = take(7 * N * D), o_Pdep_c = take(N * D),
+                 o_traj_c = take(T), o_grid = take((size_t)n_psi * D), o_dP = take(rows * D), o_est = take(N * I),
+                 o_status = take(N * I), o_steps = take(N * I), o_status_c = take(N * I), o_steps_c = take(N * I),
+                 o_idx = take(2 * N * I);
+    if (ensure_buf(p, p->mk, bytes)) return -1;
+    char *base = (char *)p->mk.d;
+    auto dd = [&](size_t o) { return (double *)(base + o); };
+    auto di = [&](size_t o) { return (int *)(base + o); };
+    HIPCK(hipMemcpyAsync(dd(o_pos), F.pos.data(), 3 * N * D, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(dd(o_dir), F.dir.data(), 3 * N * D, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(dd(o_w), F.w.data(), N * D, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(dd(o_grid), grid, (size_t)n_psi * D, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemsetAsync(dd(o_dP), 0, rows * D, s));
+    const BeamTables bt = {B, F.off.data(), F.omega.data(), F.mode.data()};
+    EntryIO e{};
+    e.n = n, e.x0 = dd(o_pos), e.N0 = dd(o_dir), e.xp = dd(o_xp), e.Np = dd(o_Np), e.s0 = dd(o_s0), e.status = di(o_est);
+    if (entry_beams_device(p, ps, bt, e, s)) return -1;
+    // (the one read-back ahead of the trace: 4 n bytes)
+    HIPCK(hipMemcpyAsync(est.data(), e.status, N * I, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    beams_compact(bc, B, F.off.data(), est.data());
+    const int m = bc.beam_off[B];
+    idx.assign(2 * N, -1);  // the gather index (m of n entries used), then its inverse
+    for (int k = 0; k < m; k++) idx[k] = bc.gather[k], idx[N + bc.gather[k]] = k;
+    HIPCK(hipMemcpyAsync(di(o_idx), idx.data(), 2 * N * I, hipMemcpyHostToDevice, s));
+    if (m > 0) {
+        const RaysGatherArgs g = {n,           m,         di(o_idx),   dd(o_pos),  dd(o_w),    dd(o_xp),   dd(o_Np),
+                                  dd(o_s0),    dd(o_pos_c), dd(o_w_c), dd(o_xp_c), dd(o_Np_c), dd(o_s0_c)};
+        hipLaunchKernelGGL(k_rays_gather, dim3(nblocks(m, 64)), dim3(64), 0, s, g);
+        HIPCK(hipGetLastError());
+    }
+    RayIO io{};
+    io.x0 = dd(o_xp_c), io.N0 = dd(o_Np_c), io.weights = dd(o_w_c), io.psi_grid = dd(o_grid);
+    io.x_launch = dd(o_pos_c), io.s0 = dd(o_s0_c), io.state = dd(o_state_c), io.status = di(o_status_c);
+    io.steps = di(o_steps_c), io.dP_shell = dd(o_dP), io.P_dep = dd(o_Pdep_c), io.traj = n_save ? dd(o_traj_c) : nullptr;
+    const BeamTables btc = {B, bc.beam_off.data(), F.omega.data(), F.mode.data()};
+    if (beams_trace_device(p, ps, cfg, btc, io, n_psi, s)) return -1;
+    const RaysScatterArgs sc = {n,           m,           n_save,        di(o_idx) + N,    di(o_est),  dd(o_state_c),
+                                dd(o_Pdep_c), dd(o_traj_c), di(o_status_c), di(o_steps_c), dd(o_state), dd(o_Pdep),
+                                dd(o_traj),  di(o_status), di(o_steps)};
+    hipLaunchKernelGGL(k_rays_scatter, dim3(nblocks(n, 64), 1 + std::min(n_save, 1024)), dim3(64), 0, s, sc);
+    HIPCK(hipGetLastError());
+    if (ddownload(out.x_plasma, dd(o_xp), 3 * N, s) || ddownload(out.N_plasma, dd(o_Np), 3 * N, s) ||
+        ddownload(out.s0, dd(o_s0), N, s) || ddownload(out.state, dd(o_state), 7 * N, s) ||
+        ddownload(out.status, di(o_status), N, s) || ddownload(out.steps, di(o_steps), N, s) ||
+        ddownload(out.P_dep, dd(o_Pdep), N, s) || ddownload(dP.data(), dd(o_dP), rows, s))
+        return -1;
+    if (n_save && ddownload(out.traj, dd(o_traj), (size_t)n_save * 5 * N, s)) return -1;
+    return torj_trace_check(p, s);
+}
+
+// ... and waited for.  A refusal or failure half-way (the workspace budget, a failed launch or
+// copy) leaves copies from and to host arrays of this call in the stream: they end before those go
+static int make_beams_device(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, const BeamFans &F,
+                             int n_psi, const double *grid, const torj_beams_rays &out, std::vector<int> &est,
+                             BeamsCompact &bc, std::vector<double> &dP) {
+    std::vector<int> idx;
+    const int rc = make_beams_enqueue(p, ps, cfg, F, n_psi, grid, out, est, bc, dP, idx);
+    if (rc && p->stream) (void)hipStreamSynchronize(p->stream);  // (the error text stays the failure's)
+    return rc;
+}
+
 extern "C" {
 
 int torj_trace_beams_device(torj_plasma_t p, const torj_trace_cfg *cfg, int n_beams, const int *beam_off,
@@ -1200,6 +1343,78 @@ int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_
     EntryIO io{};
     io.x0 = x0, io.N0 = N0, io.xp = xp, io.Np = Np, io.s0 = s0, io.status = status;
     return entry_beams_host(p, &ps, bt, io);
+}
+
+int torj_make_beams(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas, int n_beams,
+                    const torj_launcher *launchers, int N_rings, int min_azimuthal_points, const torj_trace_cfg *cfg,
+                    int n_psi, const double *grid, double *dP_dV, torj_beam_result *res, int *ray_off,
+                    const torj_beams_rays *rays) {
+    const bool count_only = !dP_dV && !res && !rays && ray_off;
+    if (!launchers) return fail("torj_make_beams: launchers is NULL");
+    if (n_beams < 1 || n_beams > kMaxBeams) return fail("torj_make_beams: n_beams must be 1..%d", kMaxBeams);
+    if (!count_only) {
+        if (!p) return fail("torj_make_beams: p is NULL");
+        if (!cfg) return fail("torj_make_beams: cfg is NULL");
+        if (!grid) return fail("torj_make_beams: psi_dP_dV is NULL");
+        if (n_psi < 2) return fail("torj_make_beams: n_psi must be >= 2");
+        if (n_plasmas < 0 || (n_plasmas == 0) != (plasmas == nullptr))
+            return fail("torj_make_beams: n_plasmas = %d with plasmas %s (n_plasmas == 0 and plasmas == NULL: every "
+                        "beam through p; else n_plasmas >= 1 listed handles)",
+                        n_plasmas, plasmas ? "given" : "NULL");
+    }
+    for (int b = 0; b < n_beams; b++) {
+        const torj_launcher &l = launchers[b];
+        if (!(l.f > 0) || !std::isfinite(l.f)) return fail("torj_make_beams: launchers[%d].f must be finite and > 0", b);
+        if (l.mode != 1 && l.mode != -1) return fail("torj_make_beams: launchers[%d].mode must be +1 (X) or -1 (O)", b);
+        if (!count_only && n_plasmas > 0 && (l.plasma < 0 || l.plasma >= n_plasmas))
+            return fail("torj_make_beams: launchers[%d].plasma = %d is outside 0..%d (n_plasmas = %d)", b, l.plasma,
+                        n_plasmas - 1, n_plasmas);
+    }
+    BeamFans F;
+    if (make_beams_fans(F, n_beams, launchers, N_rings, min_azimuthal_points, count_only)) return -1;
+    if (ray_off) std::copy(F.off.begin(), F.off.end(), ray_off);
+    if (count_only) return 0;
+    // the trace's own refusals, on the launched tables (the kept rays' are a subset): no HIP call yet
+    const PlasmaSel sel = {n_plasmas, plasmas, F.beam_pl.data()}, *ps = n_plasmas > 0 ? &sel : nullptr;
+    const torj_beams_rays out = rays ? *rays : torj_beams_rays{};
+    {
+        const BeamTables bt = {n_beams, F.off.data(), F.omega.data(), F.mode.data()};
+        const LaunchPtrs has = {true, true, true, true, true, out.traj != nullptr};
+        BeamsPlasmasPlan pp;
+        if (beams_any_plan(pp, p, ps, *cfg, bt, n_psi, has) || grid_increasing(n_psi, grid)) return -1;
+    }
+    std::vector<int> est;
+    std::vector<double> dP;
+    BeamsCompact bc;
+    if (make_beams_device(p, ps, cfg, F, n_psi, grid, out, est, bc, dP)) return -1;
+    const size_t n = (size_t)F.off[n_beams];
+    if (out.pos) std::copy(F.pos.begin(), F.pos.end(), out.pos);
+    if (out.dir) std::copy(F.dir.begin(), F.dir.end(), out.dir);
+    if (out.weights) std::copy(F.w.begin(), F.w.end(), out.weights);
+    if (out.entry_status) std::copy(est.begin(), est.begin() + n, out.entry_status);
+    // row b over the shell volumes of beam b's plasma (torj_shell_volumes' function), each plasma's once
+    std::vector<std::vector<double>> dV(ps ? n_plasmas : 1);
+    for (int b = 0; b < n_beams; b++) {
+        const double *row = dP.data() + (size_t)b * (size_t)(n_psi + 1);
+        if (dP_dV) {
+            const int j = ps ? F.beam_pl[b] : 0;
+            if (dV[j].empty()) {
+                dV[j].resize((size_t)n_psi - 1);
+                shell_volumes(ps ? plasmas[j] : p, n_psi, grid, dV[j].data());
+            }
+            double *o = dP_dV + (size_t)b * (size_t)n_psi;
+            for (int k = 0; k + 1 < n_psi; k++) o[k] = row[k] / dV[j][k];
+            o[n_psi - 1] = 0.0;
+        }
+        if (res) {
+            double w_ok = 0.0;
+            for (int i = F.off[b]; i < F.off[b + 1]; i++)
+                if (est[i] == TORJ_RAY_OK) w_ok += F.w[i];
+            res[b] = torj_beam_result{F.off[b + 1] - F.off[b], bc.n_ok[b], bc.first_bad_ray[b], bc.first_bad_status[b],
+                                      w_ok, row[n_psi]};
+        }
+    }
+    return 0;
 }
 
 int torj_power_deposition_profile(torj_plasma_t p, int n_rays, const int *n_points, const double *s,

@@ -201,3 +201,63 @@ __global__ void __launch_bounds__(64, 2) k_fit_depo_pl(FitArgs a, const BeamRec 
     const double xl[3] = {a.x_launch[i], a.x_launch[a.n + i], a.x_launch[2 * a.n + i]};
     fit_depo_ray<kOpenCache>(a, i, psi_at(pr.coef, pr.g, xl));
 }
+
+// ---- torj_make_beams: the rays that passed the ray entry closed up ahead of the trace, and the
+// trace's outputs put back in launched order behind it (torj_launch.hpp beams_compact) ----
+// m kept rays of n launched; idx[k] < n: the launched index of kept ray k
+struct RaysGatherArgs {
+    int n, m;
+    const int *idx;
+    const double *pos, *w, *xp, *Np, *s0;       // launched: 3 x n, n, 3 x n, 3 x n, n
+    double *pos_c, *w_c, *xp_c, *Np_c, *s0_c;   // kept: the same rows of m
+};
+
+// one lane per kept ray, component-major on both sides
+__global__ void __launch_bounds__(64) k_rays_gather(RaysGatherArgs a) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= a.m) return;
+    const int i = a.idx[k];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        a.pos_c[c * a.m + k] = a.pos[c * a.n + i];
+        a.xp_c[c * a.m + k] = a.xp[c * a.n + i];
+        a.Np_c[c * a.m + k] = a.Np[c * a.n + i];
+    }
+    a.w_c[k] = a.w[i];
+    a.s0_c[k] = a.s0[i];
+}
+
+// inv[i]: the kept index of launched ray i, or -1 where it failed entry: such a ray gets its
+// entry status, 0 steps, P_dep 0 and NaN in state and in its traj columns (the bytes the
+// trace's own NaN fill of traj writes)
+struct RaysScatterArgs {
+    int n, m, n_save;
+    const int *inv, *entry_status;                       // n each
+    const double *state_c, *P_dep_c, *traj_c;            // kept: 7 x m, m, n_save x 5 x m
+    const int *status_c, *steps_c;                       // m each
+    double *state, *P_dep, *traj;                        // launched: 7 x n, n, n_save x 5 x n
+    int *status, *steps;                                 // n each
+};
+
+// grid (ceil(n / 64), 1 + samples' blocks): one lane per launched ray; blockIdx.y == 0 the
+// final state, status, steps and P_dep, the others the saved samples, gridDim.y - 1 apart
+__global__ void __launch_bounds__(64) k_rays_scatter(RaysScatterArgs a) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.n) return;
+    const int k = a.inv[i];
+    const double nan = __longlong_as_double(-1ll);
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int c = 0; c < 7; c++) a.state[c * a.n + i] = k >= 0 ? a.state_c[c * a.m + k] : nan;
+        a.status[i] = k >= 0 ? a.status_c[k] : a.entry_status[i];
+        a.steps[i] = k >= 0 ? a.steps_c[k] : 0;
+        a.P_dep[i] = k >= 0 ? a.P_dep_c[k] : 0.0;
+        return;
+    }
+    for (int j = (int)blockIdx.y - 1; j < a.n_save; j += (int)gridDim.y - 1)
+#pragma unroll
+        for (int c = 0; c < 5; c++) {
+            const size_t row = (size_t)j * 5 + c;
+            a.traj[row * a.n + i] = k >= 0 ? a.traj_c[row * a.m + k] : nan;
+        }
+}

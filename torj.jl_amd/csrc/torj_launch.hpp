@@ -7,7 +7,8 @@
 // trace_device_one enqueues what the plan says, one short launcher per path;
 // trace_batched is trace_device's loop over ray batches; beams_plan and
 // beams_trace_device are the same two steps for a multi-beam launch, and
-// beams_plasmas_plan adds a plasma per beam to that plan.  trace_prologue is what
+// beams_plasmas_plan adds a plasma per beam to that plan; beams_compact closes up the
+// rays that passed the ray entry (torj_make_beams).  trace_prologue is what
 // both enqueue ahead of their trace kernels, on_caller_stream the NULL stream's
 // fork and join around either; a call's arrays reach all of them as one RayIO.
 // Also here, ahead of its first user: the Gauss-Legendre table's upload.
@@ -270,6 +271,39 @@ static int beams_plan(BeamsPlan &bp, const torj_trace_cfg &cfg, int n_beams, con
     for (int b = 0; b < n_beams; b++)
         for (int i = beam_off[b]; i < beam_off[b + 1]; i += rpw) bp.waves.push_back(BeamWave{b, i});
     return 0;
+}
+
+// ---- BeamsCompact: the rays of a multi-beam launch that passed the ray entry, closed up
+// (torj_make_beams: a ray that fails entry is reported, and the others are traced).  From
+// the launched beam_off and the n = beam_off[n_beams] entry statuses (0: entered): the
+// compacted beam_off; `gather`, the launched index of compacted ray k, in launched order
+// within each beam (stable), so a beam's kept rays sit in the waves they would sit in
+// were they launched alone; and per beam its kept count and its first failure (the ray's
+// index within the beam and its status; -1 and 0 where every ray entered).  A beam none
+// of whose rays entered becomes an empty beam, which beams_plan allows.  No HIP call.
+struct BeamsCompact {
+    std::vector<int> beam_off;  // n_beams + 1
+    std::vector<int> gather;    // beam_off[n_beams]
+    std::vector<int> n_ok, first_bad_ray, first_bad_status;  // n_beams each
+};
+
+static void beams_compact(BeamsCompact &bc, int n_beams, const int *beam_off, const int *status) {
+    bc = BeamsCompact{};
+    bc.beam_off.assign(1, 0);
+    bc.gather.reserve((size_t)beam_off[n_beams]);
+    for (int b = 0; b < n_beams; b++) {
+        int bad = -1;
+        for (int i = beam_off[b]; i < beam_off[b + 1]; i++) {
+            if (status[i] == TORJ_RAY_OK)
+                bc.gather.push_back(i);
+            else if (bad < 0)
+                bad = i;
+        }
+        bc.beam_off.push_back((int)bc.gather.size());
+        bc.n_ok.push_back(bc.beam_off[b + 1] - bc.beam_off[b]);
+        bc.first_bad_ray.push_back(bad < 0 ? -1 : bad - beam_off[b]);
+        bc.first_bad_status.push_back(bad < 0 ? 0 : status[bad]);
+    }
 }
 
 // ---- BeamsPlasmasPlan: a multi-beam launch whose beams go through differing plasmas

@@ -160,6 +160,7 @@ struct torj_plasma_s {
     size_t ev_used = 0;
     GrowBuf ws;                    // per-ray workspace (double: P_dep when the caller passes none)
     GrowBuf beams;                 // a multi-beam launch's beam and wave tables (BeamRec, BeamWave)
+    GrowBuf mk;                    // torj_make_beams: every per-ray array of a call, launched and kept
     // sticky launch error flags, ORed by every launch since the last
     // torj_trace_check (which reads and clears them): bit 0 psi grid not
     // strictly increasing, bit 1 work-queue watchdog, bit 2 unretired groups

@@ -547,6 +547,118 @@ function make_beams(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma::Vecto
     return _make_beams(p, plasmas, beam_plasma, launchers, s_max, psi_dP_dV; kw...)
 end
 
+# ---- make_beams as one C call (torj_make_beams): a ray that fails entry is reported, not fatal ----
+struct Launcher              # torj_launcher
+    r::Float64
+    phi::Float64
+    z::Float64
+    steering_angle_tor::Float64
+    steering_angle_pol::Float64
+    spot_size::Float64
+    inverse_curvature_radius::Float64
+    f::Float64
+    mode::Cint
+    plasma::Cint             # from 0: the C table's index
+end
+
+struct BeamResult            # torj_beam_result
+    n_rays::Cint
+    n_ok::Cint
+    first_bad_ray::Cint      # from 0 within the beam; -1 when every ray entered
+    first_bad_status::Cint
+    w_ok::Float64
+    deposited_power::Float64
+end
+
+struct BeamsRays             # torj_beams_rays
+    pos::Ptr{Float64}
+    dir::Ptr{Float64}
+    weights::Ptr{Float64}
+    x_plasma::Ptr{Float64}
+    N_plasma::Ptr{Float64}
+    s0::Ptr{Float64}
+    entry_status::Ptr{Cint}
+    state::Ptr{Float64}
+    status::Ptr{Cint}
+    steps::Ptr{Cint}
+    P_dep::Ptr{Float64}
+    traj::Ptr{Float64}
+end
+
+# The one call.  Its three struct pointers are typed here (Ptr{Launcher}, Ptr{BeamResult},
+# Ptr{BeamsRays}) and written with the @ccall macro; tests/test_make_beams_shim.py checks the
+# call and the three structs against the header, field by field and argument by argument.
+# `rays` is C_NULL (the count-only call: a Ptr argument may be NULL, a Ref one may not) or a
+# Ref{BeamsRays}, which the call converts to the pointer and keeps alive.
+function _torj_make_beams(p::GPUPlasma, hs, la::Vector{Launcher}, N_rings::Integer, min_az::Integer, cfg,
+                          psi_dP_dV, dP_dV, res, off::Vector{Cint}, rays)
+    return @ccall libtorj.torj_make_beams(p.h::Ptr{Cvoid}, (hs === C_NULL ? 0 : length(hs))::Cint,
+                                          hs::Ptr{Ptr{Cvoid}}, length(la)::Cint, la::Ptr{Launcher},
+                                          N_rings::Cint, min_az::Cint, cfg::Ref{TraceCfg},
+                                          length(psi_dP_dV)::Cint, psi_dP_dV::Ptr{Float64},
+                                          dP_dV::Ptr{Float64}, res::Ptr{BeamResult}, off::Ptr{Cint},
+                                          rays::Ptr{BeamsRays})::Cint
+end
+
+"""make_beams_c(p, launchers, s_max, psi_dP_dV; plasmas, beam_plasma, ...) -> (tuples, results):
+make_beams through the one C entry point.  A ray that fails entry does not throw: results[b]
+(a BeamResult) says how many of beam b's rays entered, which failed first and how much of the
+launched weight coupled, and the per-ray lists of tuples[b] are over the rays that entered, with
+their launched weights.  `beam_plasma` indexes `plasmas` from 1."""
+function make_beams_c(p::GPUPlasma, launchers, s_max::Float64, psi_dP_dV::Vector{Float64};
+                      plasmas::Union{Nothing,Vector{GPUPlasma}}=nothing,
+                      beam_plasma::Union{Nothing,Vector{<:Integer}}=nothing, ds::Float64=1e-4,
+                      N_rings::Integer=3, min_azimuthal_points::Integer=5, deposition::Integer=1,
+                      absorption::Integer=1, traj_stride::Integer=1)
+    traj_stride >= 1 || throw(ArgumentError("traj_stride must be >= 1"))
+    (plasmas === nothing) == (beam_plasma === nothing) || throw(ArgumentError("plasmas and beam_plasma go together"))
+    B = length(launchers)
+    beam_plasma === nothing || length(beam_plasma) == B || throw(ArgumentError("beam_plasma needs one entry per launcher"))
+    la = [Launcher(l[1], l[2], l[3], l[4], l[5], l[6], l[7], l[8], l[9],
+                   beam_plasma === nothing ? 0 : beam_plasma[b] - 1) for (b, l) in enumerate(launchers)]
+    hs = plasmas === nothing ? C_NULL : _handles(plasmas)
+    n_steps = max(1, round(Int, s_max / ds))
+    cfg = TraceCfg(0.0, 0, ds, n_steps, max(1, n_steps ÷ 100), 1.0, 1e-6, absorption, traj_stride, deposition,
+                   0, 1e-6, 1e-6, s_max, 100)
+    off = zeros(Cint, B + 1)
+    n_psi = length(psi_dP_dV)
+    GC.@preserve plasmas hs begin
+        check(_torj_make_beams(p, hs, la, N_rings, min_azimuthal_points, cfg, psi_dP_dV, C_NULL, C_NULL, off,
+                               C_NULL))  # the ray count
+        n, n_save = Int(off[end]), n_steps ÷ traj_stride
+        pos, dirs, w = zeros(n, 3), zeros(n, 3), zeros(n)
+        xp, Np, s0, est = zeros(n, 3), zeros(n, 3), zeros(n), zeros(Cint, n)
+        state, status, steps, Pdep = zeros(n, 7), zeros(Cint, n), zeros(Cint, n), zeros(n)
+        traj = zeros(n, 5, n_save)
+        dP_dV, res = zeros(n_psi, B), Vector{BeamResult}(undef, B)
+        GC.@preserve pos dirs w xp Np s0 est state status steps Pdep traj begin
+            rays = BeamsRays(pointer(pos), pointer(dirs), pointer(w), pointer(xp), pointer(Np), pointer(s0),
+                             pointer(est), pointer(state), pointer(status), pointer(steps), pointer(Pdep),
+                             n_save > 0 ? pointer(traj) : Ptr{Float64}(C_NULL))
+            check(_torj_make_beams(p, hs, la, N_rings, min_azimuthal_points, cfg, psi_dP_dV, dP_dV, res, off,
+                                   Ref(rays)))
+        end
+    end
+    tuples = []
+    for b in 1:B
+        arc_lengths, trajectories, ray_powers = Vector{Vector{Float64}}(), Vector{Vector{Vector{Float64}}}(), Vector{Vector{Float64}}()
+        ok = [i for i in off[b]+1:off[b+1] if est[i] == 0]
+        for i in ok
+            k = steps[i] ÷ traj_stride
+            s_i, x_i, τ_i = traj[i, 5, 1:k], [traj[i, 1:3, j] for j in 1:k], traj[i, 4, 1:k]
+            if steps[i] % traj_stride != 0  # the final state is not a saved sample
+                push!(s_i, fma(Float64(steps[i]), ds, s0[i])); push!(x_i, state[i, 1:3]); push!(τ_i, state[i, 7])
+            end
+            push!(arc_lengths, vcat(0.0, s0[i], s_i))
+            push!(trajectories, vcat([pos[i, :]], [xp[i, :]], x_i))
+            push!(ray_powers, vcat(1.0, 1.0, exp.(-τ_i)))
+        end
+        push!(tuples, (arc_lengths, trajectories, ray_powers, dP_dV[:, b], res[b].deposited_power, w[ok]))
+    end
+    return tuples, res
+end
+make_beams_c(p::TorJ.Plasma, args...; kw...) = make_beams_c(gpu_plasma(p), args...; kw...)
+
 """alpha(...) of src/general_absorption.jl:1328-1337 (repaired, DESIGN.md §3.6) at n
 points on the GPU: iwarm 1 (weakly) or 3 (fully relativistic); inv_dDdN = 1/|dD/dN|.
 Returns (alpha, N_perp^2)."""

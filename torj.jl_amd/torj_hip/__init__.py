@@ -9,13 +9,14 @@ from .physics import (abs_Al_init, abs_Albajar_fast, alpha_warm, alpha_approx, d
                       grad_lambda, gradΛ, refractive_index_sq, α_approx)
 from .plasma import B_spline, Plasma, T_e, eval_plasma, evaluate, n_e, power_deposition_profile
 from .solve import (ABSORBED, ENTRY_FAIL, LEFT_PLASMA, MAX_STEPS, NAN, OK, REFLECTED, STATUS_NAMES,
-                    RayEntryError, TraceResult, make_beam, make_beams, make_ray, ray_entry, ray_entry_beams,
-                    trace, trace_beams)
+                    RayEntryError, TraceResult, make_beam, make_beams, make_beams_c, make_ray,
+                    ray_entry, ray_entry_beams, trace, trace_beams)
 
 __all__ = [
     "Plasma", "evaluate", "B_spline", "n_e", "T_e", "eval_plasma", "refractive_index_sq",
     "dispersion_relation", "gradΛ", "grad_lambda", "abs_Al_init", "abs_Albajar_fast", "alpha_warm",
     "α_approx", "alpha_approx", "launch_peripheral_rays", "pol_tor_angles_2_vector",
-    "make_ray", "make_beam", "ray_entry", "trace", "trace_beams", "ray_entry_beams", "make_beams", "TraceResult", "RayEntryError", "TorjError",
+    "make_ray", "make_beam", "ray_entry", "trace", "trace_beams", "ray_entry_beams", "make_beams", "make_beams_c",
+    "TraceResult", "RayEntryError", "TorjError",
     "build", "lib", "LIB_PATH", "EXPORTED", "STATUS_NAMES", "power_deposition_profile",
 ]

@@ -51,6 +51,27 @@ class BeamShard(C.Structure):
                 ("counters", C.c_void_p)]
 
 
+class Launcher(C.Structure):
+    """torj_launcher: make_beam's leading arguments, and the beam's index into plasmas[]"""
+    _fields_ = [("r", C.c_double), ("phi", C.c_double), ("z", C.c_double),
+                ("steering_angle_tor", C.c_double), ("steering_angle_pol", C.c_double),
+                ("spot_size", C.c_double), ("inverse_curvature_radius", C.c_double), ("f", C.c_double),
+                ("mode", C.c_int), ("plasma", C.c_int)]
+
+
+class BeamResult(C.Structure):
+    """torj_beam_result"""
+    _fields_ = [("n_rays", C.c_int), ("n_ok", C.c_int), ("first_bad_ray", C.c_int),
+                ("first_bad_status", C.c_int), ("w_ok", C.c_double), ("deposited_power", C.c_double)]
+
+
+class BeamsRays(C.Structure):
+    """torj_beams_rays: torj_make_beams' per-ray host arrays, each may be NULL"""
+    _fields_ = [("pos", _dp), ("dir", _dp), ("weights", _dp), ("x_plasma", _dp), ("N_plasma", _dp),
+                ("s0", _dp), ("entry_status", _ip), ("state", _dp), ("status", _ip), ("steps", _ip),
+                ("P_dep", _dp), ("traj", _dp)]
+
+
 _SIGS = {
     "torj_abi_version": (C.c_int, []),
     "torj_build_id": (C.c_char_p, []),
@@ -136,6 +157,10 @@ _SIGS = {
                                             [C.c_void_p] * 7),
     "torj_ray_entry_beams_plasmas_gpu": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.c_int, _ip, _dp, _ip, _dp,
                                                    _dp, _dp, _dp, _dp, _ip]),
+    # make_beams as one call: launchers in, per-beam results and per-ray arrays out (all host)
+    "torj_make_beams": (C.c_int, [C.c_void_p, C.c_int, _hp, C.c_int, C.POINTER(Launcher), C.c_int, C.c_int,
+                                  C.POINTER(TraceCfg), C.c_int, _dp, _dp, C.POINTER(BeamResult), _ip,
+                                  C.POINTER(BeamsRays)]),
     "torj_shell_volumes": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "torj_power_deposition_profile": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp,
                                                 _dp, _dp]),

@@ -12,7 +12,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import TraceCfg, TorjError, check, dptr, f64, handles, iptr, lib, soa
+from ._lib import (BeamResult, BeamsRays, Launcher, TraceCfg, TorjError, check, dptr, f64, handles, iptr, lib,
+                   soa)
 from .launch import launch_peripheral_rays, pol_tor_angles_2_vector
 
 OK, LEFT_PLASMA, ABSORBED, NAN, REFLECTED, ENTRY_FAIL, MAX_STEPS = range(7)
@@ -376,3 +377,77 @@ def make_beams(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, 
         lists = _ray_lists(res, range(off[b], off[b + 1]), pos, xp, s0, ds, traj_stride)
         out.append((*lists, dP_dV, float(res.dP_shell[b, len(g)]), w[off[b]:off[b + 1]]))
     return out
+
+
+def _launcher_table(launchers, beam_plasma):
+    la = (Launcher * len(launchers))()
+    for b, (r, phi, z, tor, pol, spot, inv_curv, f, m) in enumerate(launchers):
+        la[b] = Launcher(float(r), float(phi), float(z), float(tor), float(pol), float(spot), float(inv_curv),
+                         float(f), int(m), int(beam_plasma[b]) if beam_plasma is not None else 0)
+    return la
+
+
+def make_beams_arrays(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, traj_stride: int = 1,
+                      deposition: str = "reference", absorption="albajar", plasmas=None, beam_plasma=None,
+                      N_rings: int = 3, min_azimuthal_points: int = 5) -> dict:
+    """torj_make_beams as it is, two calls (the ray count, then the arrays): a dict of
+    `off` (n_beams + 1 launched offsets), `results` (n_beams dicts of torj_beam_result's
+    fields), `dP_dV` (n_beams, n_psi), the launch's `pos`, `dirs` (n, 3) and `w` (n,),
+    the entry's `xp`, `Np` (n, 3), `s0` and `entry_status` (n,), and `res`, a
+    TraceResult over all n launched rays (dP_shell None), all in launched order."""
+    if (plasmas is None) != (beam_plasma is None):
+        raise ValueError("plasmas and beam_plasma go together")
+    B = len(launchers)
+    if beam_plasma is not None and len(beam_plasma) != B:
+        raise ValueError("beam_plasma needs n_beams entries")
+    la = _launcher_table(launchers, beam_plasma)
+    hs, n_pl = (handles(plasmas), len(plasmas)) if plasmas is not None else (None, 0)
+    n_steps = _steps_for(s_max, ds)
+    cfg = TraceCfg(0.0, 0, float(ds), n_steps, max(1, n_steps // 100), 1.0, 1e-6, _absorption_code(absorption),
+                   int(traj_stride), DEPOSITION[deposition])
+    g = f64(psi_dP_dV)
+    off = np.zeros(B + 1, dtype=np.int32)
+    head = (plasma.handle, n_pl, hs, B, la, int(N_rings), int(min_azimuthal_points), cfg, len(g), dptr(g))
+    rc = lib().torj_make_beams(*head, None, None, iptr(off), None)
+    if rc != 0 and lib().torj_last_error().decode().startswith("ArgumentError"):
+        raise ValueError(lib().torj_last_error().decode())
+    check(rc)
+    n = int(off[B])
+    n_save = n_steps // traj_stride if traj_stride > 0 else 0
+    a = dict(pos=np.zeros((3, n)), dir=np.zeros((3, n)), weights=np.zeros(n), x_plasma=np.zeros((3, n)),
+             N_plasma=np.zeros((3, n)), s0=np.zeros(n), entry_status=np.zeros(n, dtype=np.int32),
+             state=np.zeros((7, n)), status=np.zeros(n, dtype=np.int32), steps=np.zeros(n, dtype=np.int32),
+             P_dep=np.zeros(n), traj=np.zeros((n_save, 5, n)) if n_save > 0 else None)
+    rays = BeamsRays(*[iptr(a[k]) if k in ("entry_status", "status", "steps") else dptr(a[k])
+                       for k, _ in BeamsRays._fields_])
+    dP_dV = np.zeros((B, len(g)))
+    res = (BeamResult * B)()
+    check(lib().torj_make_beams(*head, dptr(dP_dV), res, iptr(off), rays))
+    traj = a["traj"].transpose(2, 0, 1).copy() if a["traj"] is not None else None
+    return dict(off=off, dP_dV=dP_dV, results=[{k: getattr(r, k) for k, _ in BeamResult._fields_} for r in res],
+                pos=a["pos"].T.copy(), dirs=a["dir"].T.copy(), w=a["weights"], xp=a["x_plasma"].T.copy(),
+                Np=a["N_plasma"].T.copy(), s0=a["s0"], entry_status=a["entry_status"],
+                res=TraceResult(a["state"].T.copy(), a["status"], a["steps"], None, a["P_dep"], traj))
+
+
+def make_beams_c(plasma, launchers, s_max: float, psi_dP_dV, *, ds: float = 1e-4, traj_stride: int = 1,
+                 deposition: str = "reference", absorption="albajar", plasmas=None, beam_plasma=None,
+                 N_rings: int = 3, min_azimuthal_points: int = 5):
+    """make_beams through the one C entry point torj_make_beams -> (tuples, results).
+    tuples[b] is make_beam's 6-tuple of launcher b built from the call's per-ray
+    arrays; where every ray enters it equals make_beams'.  A ray that fails entry
+    does not raise: the per-ray lists of tuples[b] (arc lengths, trajectories, ray
+    powers, weights) are over the rays that entered, with their launched weights
+    (not renormalised), and results[b] holds torj_beam_result's fields: n_rays,
+    n_ok, first_bad_ray and first_bad_status within the beam (-1, 0 when all
+    entered), w_ok, deposited_power."""
+    m = make_beams_arrays(plasma, launchers, s_max, psi_dP_dV, ds=ds, traj_stride=traj_stride,
+                          deposition=deposition, absorption=absorption, plasmas=plasmas, beam_plasma=beam_plasma,
+                          N_rings=N_rings, min_azimuthal_points=min_azimuthal_points)
+    off, st = m["off"], m["entry_status"]
+    tuples = []
+    for b, r in enumerate(m["results"]):
+        ok = off[b] + np.flatnonzero(st[off[b]:off[b + 1]] == OK)
+        lists = _ray_lists(m["res"], ok, m["pos"], m["xp"], m["s0"], ds, traj_stride)
+        tuples.append((*lists, m["dP_dV"][b].copy(), float(r["deposited_power"]), m["w"][ok]))
+    return tuples, m["results"]
