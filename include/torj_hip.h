@@ -48,7 +48,9 @@ extern "C" {
                                torj_plasma_get_cell_table;
                                still 8 (three more symbols, nothing changed): torj_plasma_update_gpu,
                                torj_plasma_update_profiles_gpu, torj_plasma_update_device;
-                               still 8 (one more symbol, nothing changed): torj_make_beams */
+                               still 8 (one more symbol, nothing changed): torj_make_beams;
+                               still 8 (two more symbols, nothing changed): torj_ray_profile,
+                               torj_ray_profile_device */
 
 /* per-ray status codes (replace the reference's @assert / unhandled returns) */
 enum torj_status {
@@ -467,6 +469,77 @@ int torj_ray_entry_beams_plasmas_gpu(torj_plasma_t p, int n_plasmas, const torj_
                                      const double *omega, const int *mode, const double *x0,
                                      const double *N0, double *x_plasma, double *N_plasma,
                                      double *s0, int *status);
+
+/* ---- ray profiles: N, the plasma parameters and alpha at every saved point of a ray ----
+ * What the reference computes along a ray and its validation reads point by point
+ * (test/tests/test_trajectory.jl, test_absorption.jl): the rays of n_beams small
+ * beams are traced as torj_trace_beams[_plasmas] traces them without deposition, and
+ * per saved point one row of TORJ_PROF_NCOL columns is written, each column the named
+ * reference function at the row's (x, N) with the beam's omega and mode and the
+ * beam's plasma.
+ * Beams: beam_off, omega, mode (HOST tables, consumed before the call returns) as in
+ * torj_trace_beams, empty beams allowed, a single beam is n_beams = 1.  n_plasmas == 0
+ * and plasmas == NULL send every beam through p (as torj_make_beams); else beam b goes
+ * through plasmas[beam_plasma[b]] under torj_trace_beams_plasmas' rules.
+ * cfg is read as torj_trace_beams reads it (ds, n_steps, chunk_steps, psi_exit, P_min,
+ * absorption, traj_stride, integrator; omega and mode are the beams'); deposition is
+ * not read.  s0 (n, the arc length at the entry point) may be NULL: s then counts from
+ * the entry point.  Restrictions are torj_trace_beams': absorption 0 / 1, integrator 0,
+ * torj_set_sched -1 / 0 / 2; lanes per ray are chosen as there.
+ * prof: n_rows x TORJ_PROF_NCOL x n doubles, n = beam_off[n_beams], rows slowest, a
+ * column contiguous over the rays (traj's layout): prof[(k * TORJ_PROF_NCOL + c) * n + i].
+ * n_rows must equal n_steps / traj_stride + 1.  Row 0 is the entry point (step 0), row k
+ * step k * traj_stride, so traj's sample k - 1 is row k.  Row k of ray i is written iff
+ * k * traj_stride <= steps[i]; every other row of that ray is NaN in all columns.
+ * state, status, steps: torj_trace_beams' outputs, each may be NULL.  With the same
+ * lanes per ray they, and columns 0-2, 6, 7 against traj, are what torj_trace_beams
+ * gives bit for bit (the trace kernel is k_trace_beams' code).  Columns ALPHA and DP_DS
+ * are torj_dispersion's alpha at the row's (x, N): abs_Albajar_fast chooses per wave of
+ * 64 rays of a row, so between launches of differing rays they agree to the alpha bar
+ * (1e-10 relative), not to the bit; every other column does not depend on the other rays.
+ * Refusals come before any device work: torj_trace_beams' by their texts; the call's
+ * own start with "torj_ray_profile:" and name the argument (prof NULL, traj_stride < 1,
+ * n_steps < 1, n_rows with the expected value).
+ * A warm alpha along the cold-traced ray is one further call: columns X_PL, Y_PL, N_ABS,
+ * N_PAR, TE (18, 19, 21, 20, 13) and the reciprocal of column DLAMBDA_DN (24) are
+ * torj_alpha_warm's inputs
+ * X, Y, N_abs, N_par, Te, inv_dDdN.
+ * _device: every pointer but the host tables is device memory; enqueued on `stream`
+ * as torj_trace_beams_device is (NULL stream, torj_timing: the trace, then the point
+ * kernel; one stream per handle: the tables go through the handle's scratch; check
+ * with torj_trace_check).  torj_ray_profile: host pointers, synchronous, checked; it
+ * allocates the table on the device for the call (failure is an error naming the
+ * byte count). */
+enum {
+    TORJ_PROF_X = 0, TORJ_PROF_Y, TORJ_PROF_Z, /* 0-2: the point x, y, z [m] */
+    TORJ_PROF_NX, TORJ_PROF_NY, TORJ_PROF_NZ,      /* 3-5: the refractive index vector N */
+    TORJ_PROF_TAU,      /* 6: optical depth */
+    TORJ_PROF_S,        /* 7: arc length as traj stores it, s0 + step * ds */
+    TORJ_PROF_P,        /* 8: P = exp(-tau) */
+    TORJ_PROF_ALPHA,    /* 9: alpha_approx(x, N) (src/absorption.jl:228-235); 0 for absorption = 0 */
+    TORJ_PROF_DP_DS,    /* 10: dP/ds = P alpha (src/solve.jl:171), also in row 0: make_ray's leading 0
+                           there (src/solve.jl:151) is its padding, not alpha, and is not imitated */
+    TORJ_PROF_PSI,      /* 11: evaluate(psi_norm_spline, x) */
+    TORJ_PROF_NE, TORJ_PROF_TE,                    /* 12, 13: n_e [m^-3], T_e [eV] */
+    TORJ_PROF_BX, TORJ_PROF_BY, TORJ_PROF_BZ,      /* 14-16: B_spline [T] */
+    TORJ_PROF_B_ABS,    /* 17: |B| */
+    TORJ_PROF_X_PL, TORJ_PROF_Y_PL, TORJ_PROF_N_PAR, /* 18-20: X, Y, N_par of eval_plasma */
+    TORJ_PROF_N_ABS,    /* 21: |N| */
+    TORJ_PROF_NS2,      /* 22: refractive_index_sq(X, Y, N_par, mode): the cold index the ray should sit on */
+    TORJ_PROF_LAMBDA,   /* 23: dispersion_relation(x, N): the integrator's drift off Lambda = 0 */
+    TORJ_PROF_DLAMBDA_DN, /* 24: |dLambda/dN|, gradLambda!'s normalisation (src/solve.jl:91) */
+    TORJ_PROF_NCOL      /* 25 */
+};
+int torj_ray_profile_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                            const int *beam_plasma, const torj_trace_cfg *cfg, int n_beams,
+                            const int *beam_off, const double *omega, const int *mode,
+                            const double *x0, const double *N0, const double *s0, int n_rows,
+                            double *prof, double *state, int *status, int *steps, void *stream);
+int torj_ray_profile(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
+                     const int *beam_plasma, const torj_trace_cfg *cfg, int n_beams,
+                     const int *beam_off, const double *omega, const int *mode, const double *x0,
+                     const double *N0, const double *s0, int n_rows, double *prof, double *state,
+                     int *status, int *steps);
 
 /* ---- make_beams: many launchers in one call; failed entries reported ---------
  * make_beam (src/solve.jl:209-242) for n_beams launchers at once, the five-call

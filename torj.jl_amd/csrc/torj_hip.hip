@@ -1323,6 +1323,58 @@ int torj_trace_beams_plasmas(torj_plasma_t p, int n_plasmas, const torj_plasma_t
     return beams_host_entry(p, &ps, cfg, bt, io, n_psi);
 }
 
+// ---- ray profiles: one row of TORJ_PROF_NCOL columns per saved point of every ray (profile_device) ----
+static_assert(kProfCols == TORJ_PROF_NCOL, "the kernels' row width is the header's");
+
+int torj_ray_profile_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas, const int *beam_plasma,
+                            const torj_trace_cfg *cfg, int n_beams, const int *beam_off, const double *omega,
+                            const int *mode, const double *x0, const double *N0, const double *s0, int n_rows,
+                            double *prof, double *state, int *status, int *steps, void *stream) {
+    const PlasmaSel ps = {n_plasmas, plasmas, beam_plasma};
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    RayIO io{};
+    io.x0 = x0, io.N0 = N0, io.s0 = s0, io.state = state, io.status = status, io.steps = steps;
+    return profile_device(p, n_plasmas == 0 && !plasmas ? nullptr : &ps, cfg, bt, io, n_rows, prof, stream);
+}
+
+// host pointers, synchronous, checked: the table lives on the device for the call
+int torj_ray_profile(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas, const int *beam_plasma,
+                     const torj_trace_cfg *cfg, int n_beams, const int *beam_off, const double *omega,
+                     const int *mode, const double *x0, const double *N0, const double *s0, int n_rows,
+                     double *prof, double *state, int *status, int *steps) {
+    const PlasmaSel sel = {n_plasmas, plasmas, beam_plasma};
+    const PlasmaSel *ps = n_plasmas == 0 && !plasmas ? nullptr : &sel;
+    const BeamTables bt = {n_beams, beam_off, omega, mode};
+    RayIO h{};
+    h.x0 = x0, h.N0 = N0, h.s0 = s0, h.state = state, h.status = status, h.steps = steps;
+    {
+        BeamsPlasmasPlan pp;  // argument errors before any device work (the device form repeats them on its pointers)
+        if (profile_plan(pp, p, ps, cfg, bt, h, n_rows, prof)) return -1;
+    }
+    const size_t n = (size_t)beam_off[n_beams], cells = (size_t)n_rows * TORJ_PROF_NCOL * n;
+    if (n == 0) return 0;
+    if (ensure_device(p)) return -1;
+    hipStream_t s = p->stream;
+    DevBufs B;
+    RayIO d{};
+    if (B.up(&d.x0, h.x0, 3 * n, s) || B.up(&d.N0, h.N0, 3 * n, s) || B.up(&d.s0, h.s0, n, s)) return -1;
+    if (B.alloc(&d.state, 7 * n, h.state != nullptr) || B.alloc(&d.status, n, h.status != nullptr) ||
+        B.alloc(&d.steps, n, h.steps != nullptr))
+        return -1;
+    double *d_prof = nullptr;
+    if (hipMalloc(&d_prof, cells * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("torj_ray_profile: no device memory for the table of %zu bytes (%d rows x %d columns x %zu rays)",
+                    cells * sizeof(double), n_rows, TORJ_PROF_NCOL, n);
+    }
+    B.track(d_prof);
+    if (profile_device(p, ps, cfg, bt, d, n_rows, d_prof, s)) return -1;
+    if (ddownload(prof, d_prof, cells, s) || ddownload(h.state, d.state, 7 * n, s) ||
+        ddownload(h.status, d.status, n, s) || ddownload(h.steps, d.steps, n, s))
+        return -1;
+    return torj_trace_check(p, s);
+}
+
 int torj_ray_entry_beams_plasmas_device(torj_plasma_t p, int n_plasmas, const torj_plasma_t *plasmas,
                                         const int *beam_plasma, int n_beams, const int *beam_off,
                                         const double *omega, const int *mode, const double *x0, const double *N0,

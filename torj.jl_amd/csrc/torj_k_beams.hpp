@@ -20,6 +20,8 @@
 // not one function with them: a shared __forceinline__ body is optimised on its own
 // before it is inlined and gave those kernels other registers and schedules
 // (profiles/r14/kernels_asm.txt).  A fix to one of the four is made there and here.
+// Ray profiles (torj_ray_profile[_device]): k_profile_beams, k_trace_beams' body storing
+// (x, N, tau, s) per saved point, and k_profile_pts, the rest of each stored row.
 // (a slice of torj_hip.hip: included after `using namespace torj`)
 #pragma once
 #include "torj_args.hpp"
@@ -121,6 +123,89 @@ __global__ void __launch_bounds__(64) k_final_alpha_beams(BA ba) {
     }
     if constexpr (ABS != 0) ray_rhs_m<ABS>(ab.coef, ab.g, ab.k, c_gl, ab.omega, ab.mode, a.abs_model, x, N, du, al, nullptr);
     a.smp_dpds[smp_at(k, i, a.smp_rows)] = exp(-a.state[6 * a.n + i]) * al;
+}
+
+// ---- ray profiles (torj_ray_profile[_device]): one row of kProfCols columns per saved point
+// of a ray, prof[(row * kProfCols + c) * n + i], NaN-filled before the two kernels below ----
+// Stage A, the latency chain: k_trace_beams' body without deposition.  Lane sub == 0 stores
+// (x, N, tau, s) of row 0 ahead of the loop and of row steps / traj_stride where the trace
+// stores a trajectory sample (ray_segment's PROF): nothing is evaluated for the table here.
+// grid: the wave table's entries; 64 lanes
+template <int ABS, int LPR, class BA>
+__global__ void __launch_bounds__(64, TORJ_MIN_WAVES) k_profile_beams(BA ba, double *prof) {
+    const BeamWave wv = ba.waves[blockIdx.x];
+    const BeamRec br = ba.beams[wv.beam];
+    const TraceArgs a = beam_args(ba, wv.beam, br);
+    const int i = wv.first + (int)threadIdx.x / LPR, sub = (int)threadIdx.x % LPR;
+    AlbajarWork work = {};
+    unsigned long long steps = 0;
+    if (i < br.hi) {
+        RayState r;
+        load_start(a, i, r);
+        if (sub == 0) profile_store(prof, a, i, 0, r.x, r.N, r.tau, 0);
+        ray_segment<ABS, kDepoNone, false, LPR, true>(a, i, 1.0, r, a.n_steps, work, sub, prof);
+        if (sub == 0) {
+            store_state(a, i, r);
+            steps = r.steps;
+        }
+    }
+    flush_counters(a, steps, 4ull * steps, work);
+}
+
+// Stage B, fully parallel: one lane per (row, ray), grid (ceil(n / 64), n_rows), the ray index
+// fastest.  A row the trace did not reach keeps its NaN fill; a stored one gets columns 8-24
+// from its (x, N) with the ray's beam's constants and plasma: the device functions of
+// k_eval_plasma, k_dispersion<true> and k_refr.  alpha is alpha_approx as k_dispersion gives
+// it (every harmonic evaluated, no tiny-alpha skip); ABS 0: alpha = 0.
+// T: the ray's entry of column 0 of one row; ab: its beam's arguments
+template <int ABS>
+__device__ __forceinline__ void profile_row(const TraceArgs &ab, double *T, size_t n) {
+    double x[3], N[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        x[c] = T[c * n];
+        N[c] = T[(3 + c) * n];
+    }
+    if (x[0] != x[0]) return;
+    PlasmaPoint p;
+    plasma_point<true>(ab.coef, ab.g, ab.k, x, p);
+    double du[6], Npar, inv;
+    const double D = dispersion_grad(p, N, ab.mode, du, &Npar, &inv);
+    const double Nabs = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
+    const double Te = exp(p.lnTe);
+    double al = 0.0;
+    if constexpr (ABS != 0) al = abs_albajar_fast(c_gl, ab.omega, p.X, p.Y, Nabs, Npar, Te, ab.mode, nullptr);
+    const double P = exp(-T[6 * n]);
+    T[8 * n] = P;
+    T[9 * n] = al;
+    T[10 * n] = P * al;
+    T[11 * n] = eval_one(ab.coef, ab.g, sqrt(x[0] * x[0] + x[1] * x[1]), x[2], F_PSI);
+    T[12 * n] = p.ne;
+    T[13 * n] = Te;
+    T[14 * n] = p.B[0];
+    T[15 * n] = p.B[1];
+    T[16 * n] = p.B[2];
+    T[17 * n] = p.Babs;
+    T[18 * n] = p.X;
+    T[19 * n] = p.Y;
+    T[20 * n] = Npar;
+    T[21 * n] = Nabs;
+    T[22 * n] = refractive_index_sq(p.X, p.Y, Npar, ab.mode);
+    T[23 * n] = D;
+    T[24 * n] = 1.0 / inv;
+}
+
+template <int ABS, class BA>
+__global__ void __launch_bounds__(64) k_profile_pts(BA ba, double *prof, int n_rows) {
+    const TraceArgs &a = ba.a;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.n) return;
+    const size_t n = (size_t)a.n;
+    const int b = beam_of(ba.beams, ba.n_beams, i);
+    const TraceArgs ab = beam_args(ba, b, ba.beams[b]);
+    // (rows beyond the grid's y extent of 65 535: the block's next rows)
+    for (int row = blockIdx.y; row < n_rows; row += gridDim.y)
+        profile_row<ABS>(ab, prof + (size_t)row * kProfCols * n + i, n);
 }
 
 // k_shell_sum per beam: grid (n_psi, n_beams), block (k, b) sums beam b's rays into

@@ -98,6 +98,22 @@ struct RayState {
     int status, steps;
 };
 
+// A ray profile's table (torj_ray_profile, torj_k_beams.hpp): row `row` of ray i is
+// prof[(row * kProfCols + c) * n + i].  The trace stores columns 0-7 of a saved
+// point: x, N, tau and the arc length in the form the trajectory samples have it.
+constexpr int kProfCols = 25;
+__device__ __forceinline__ void profile_store(double *prof, const TraceArgs &a, int i, int row, const double x[3],
+                                              const double N[3], double tau, int steps) {
+    double *T = prof + (size_t)row * kProfCols * (size_t)a.n + i;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        T[c * (size_t)a.n] = x[c];
+        T[(3 + c) * (size_t)a.n] = N[c];
+    }
+    T[6 * (size_t)a.n] = tau;
+    T[7 * (size_t)a.n] = (a.s0 ? a.s0[i] : 0.0) + steps * a.ds;
+}
+
 // Integrate one ray from its current step to `s_end` (the make_ray loop,
 // src/solve.jl:154-177): classic RK4 of sys!, optical depth, chunk-boundary
 // termination, shell deposition, trajectory samples.  Shared by the one-shot
@@ -105,9 +121,11 @@ struct RayState {
 // LPR > 1: the ray's LPR lanes integrate it together (identical state in every
 // lane; the absorption's node pairs are split between them) and lane sub = 0
 // does the ray's stores.
-template <int ABS, int DEPO, bool TRAJ, int LPR = 1>
+// PROF (k_profile_beams): the saved points' (x, N, tau, s) into the rows of `prof`
+// (profile_store) where TRAJ stores a sample; off, the code is what it was.
+template <int ABS, int DEPO, bool TRAJ, int LPR = 1, bool PROF = false>
 __device__ __forceinline__ void ray_segment(const TraceArgs &a, int i, double w, RayState &r,
-                                            int s_end, AlbajarWork &work, int sub = 0) {
+                                            int s_end, AlbajarWork &work, int sub = 0, double *prof = nullptr) {
     static_assert(LPR == 1 || (ABS == 1 && DEPO != kDepoBinned), "lanes per ray: Albajar, no binning");
     const bool wr = LPR == 1 || sub == 0;
     const GLTable &gl = c_gl;
@@ -199,6 +217,10 @@ __device__ __forceinline__ void ray_segment(const TraceArgs &a, int i, double w,
                 T[3 * (size_t)a.n] = tau;
                 T[4 * (size_t)a.n] = (a.s0 ? a.s0[i] : 0.0) + r.steps * a.ds;
             }
+        }
+        if constexpr (PROF) {
+            if (wr && a.traj_stride > 0 && (r.steps % a.traj_stride) == 0)
+                profile_store(prof, a, i, r.steps / a.traj_stride, x, N, tau, r.steps);
         }
         if (check) {
             if (psi_b > a.psi_exit) {  // src/solve.jl:174

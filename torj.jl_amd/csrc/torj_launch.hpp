@@ -755,6 +755,93 @@ static int beams_trace_device(torj_plasma_t p, const PlasmaSel *ps, const torj_t
     });
 }
 
+// ---- ray profiles (torj_ray_profile[_device]; torj_k_beams.hpp k_profile_beams, k_profile_pts) ----
+// the call's own refusals and then the multi-beam plan's, on a cfg whose deposition is not
+// read: no HIP call.  io: x0, N0, s0 and whichever of state, status, steps the caller gives.
+static int profile_plan(BeamsPlasmasPlan &pp, const torj_plasma_s *p, const PlasmaSel *ps, const torj_trace_cfg *cfg,
+                        const BeamTables &bt, const RayIO &io, int n_rows, const double *prof) {
+    if (!p) return fail("torj_ray_profile: p is NULL");
+    if (!cfg) return fail("torj_ray_profile: cfg is NULL");
+    if (!prof) return fail("torj_ray_profile: prof is NULL");
+    if (cfg->traj_stride < 1) return fail("torj_ray_profile: traj_stride = %d < 1", cfg->traj_stride);
+    if (cfg->n_steps < 1) return fail("torj_ray_profile: n_steps = %d < 1", cfg->n_steps);
+    if (n_rows != cfg->n_steps / cfg->traj_stride + 1)
+        return fail("torj_ray_profile: n_rows = %d, but n_steps / traj_stride + 1 = %d", n_rows,
+                    cfg->n_steps / cfg->traj_stride + 1);
+    torj_trace_cfg c = *cfg;
+    c.deposition = 0;
+    const LaunchPtrs has = {io.x0 && io.N0, false, false, false, io.s0 != nullptr, false};
+    return beams_any_plan(pp, p, ps, c, bt, 0, has);
+}
+
+template <class BA>
+static int launch_profile(const BA &ba, const BeamsPlan &bp, double *prof, int n_rows, hipEvent_t ev[3],
+                          hipStream_t s) {
+    const dim3 grd((unsigned)bp.waves.size()), blk(64);
+    if (bp.lpr == 16)
+        hipLaunchKernelGGL((k_profile_beams<1, 16, BA>), grd, blk, 0, s, ba, prof);
+    else if (ba.a.abs_model == 1)
+        hipLaunchKernelGGL((k_profile_beams<1, 1, BA>), grd, blk, 0, s, ba, prof);
+    else
+        hipLaunchKernelGGL((k_profile_beams<0, 1, BA>), grd, blk, 0, s, ba, prof);
+    HIPCK(hipGetLastError());
+    if (ev[1]) HIPCK(hipEventRecord(ev[1], s));
+    const dim3 grdB((unsigned)nblocks(ba.a.n, 64), (unsigned)std::min(n_rows, 65535));
+    if (ba.a.abs_model == 1)
+        hipLaunchKernelGGL((k_profile_pts<1, BA>), grdB, blk, 0, s, ba, prof, n_rows);
+    else
+        hipLaunchKernelGGL((k_profile_pts<0, BA>), grdB, blk, 0, s, ba, prof, n_rows);
+    HIPCK(hipGetLastError());
+    if (ev[2]) HIPCK(hipEventRecord(ev[2], s));
+    return 0;
+}
+
+// one profile launch on the caller's stream (the body of torj_ray_profile_device): the table's
+// NaN fill, the trace that stores (x, N, tau, s) per saved point, then the point kernel that
+// fills the rest of every stored row.  The host tables are consumed before it returns.  No
+// kernel of the launch sets a sticky flag (no psi grid, no work queue): torj_trace_check
+// after it waits for the stream and reports what earlier launches left.  torj_timing: the
+// trace is the trace phase, the point kernel the phase after it.
+static int profile_device(torj_plasma_t p, const PlasmaSel *ps, const torj_trace_cfg *cfg, const BeamTables &bt,
+                          const RayIO &caller, int n_rows, double *prof, void *stream) {
+    BeamsPlasmasPlan pp;
+    const BeamsPlan &bp = pp.bp;
+    const bool fresh = !p || !p->d_flags;
+    if (profile_plan(pp, p, ps, cfg, bt, caller, n_rows, prof)) return -1;
+    return on_caller_stream(p, stream, [&](hipStream_t s) -> int {
+        if (p->timing) p->timing_calls++;
+        if (ensure_devices(p, ps)) return -1;
+        if ((fresh || ps) && profile_plan(pp, p, ps, cfg, bt, caller, n_rows, prof)) return -1;
+        RayIO io = caller;
+        const int n = io.n = bp.n;
+        if (n == 0) return 0;
+        if (cfg->absorption == 1 && ensure_gl_on_device(p->device)) return -1;
+        // the final state, status and steps the caller does not ask for: the handle's per-ray workspace
+        if (!io.state || !io.status || !io.steps) {
+            if (ensure_buf(p, p->ws, (size_t)n * (7 * sizeof(double) + 2 * sizeof(int)))) return -1;
+            double *w = (double *)p->ws.d;
+            if (!io.state) io.state = w;
+            if (!io.status) io.status = (int *)(w + 7 * (size_t)n);
+            if (!io.steps) io.steps = (int *)(w + 7 * (size_t)n) + n;
+        }
+        BeamsPlArgs pa{};
+        BeamsArgs &ba = pa;
+        torj_trace_cfg c1 = *cfg;  // (omega and mode are the beams'; any valid pair here)
+        c1.omega = bt.omega[0], c1.mode = bt.mode[0];
+        TraceArgs &a = ba.a = trace_args(p, c1, io);
+        a.traj_stride = cfg->traj_stride;  // the rows' stride; a.traj stays null
+        ba.n_beams = bt.n_beams;
+        if (beams_upload(p, bp.beams, bp.waves, pp.plasmas, pp.beam_pl, s, &ba.beams, &ba.waves, &pa.plasmas,
+                         &pa.beam_pl))
+            return -1;
+        // NaN, the bytes of the trace's own fill of traj
+        HIPCK(hipMemsetAsync(prof, 0xFF, (size_t)n_rows * kProfCols * (size_t)n * sizeof(double), s));
+        hipEvent_t ev[3];
+        if (timing_begin(p, ev, s)) return -1;
+        return ps ? launch_profile(pa, bp, prof, n_rows, ev, s) : launch_profile(ba, bp, prof, n_rows, ev, s);
+    });
+}
+
 // ---- ray batches (trace_device): the beam in contiguous batches of nb
 // rays, each its own trace_device_one; the batch's inputs gathered into and its
 // outputs scattered from compact staging ----

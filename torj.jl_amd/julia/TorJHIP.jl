@@ -496,6 +496,39 @@ function trace_beams(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma0::Vec
     return state, status, steps, dP, Pdep, traj
 end
 
+# ---- ray profiles (torj_ray_profile): N, the plasma parameters and alpha at every saved point ----
+# the columns of a row, in the order of the header's TORJ_PROF_* enum
+const PROFILE_COLUMNS = (:x, :y, :z, :Nx, :Ny, :Nz, :tau, :s, :P, :alpha, :dP_ds, :psi, :ne, :Te, :Bx, :By, :Bz,
+                         :B_abs, :X, :Y, :N_par, :N_abs, :Ns2, :Lambda, :dLambda_dN)
+
+"""ray_profile(p, cfg, beam_off, omega, mode, x0, N0; s0, plasmas, beam_plasma0) -- the rays of the
+concatenated beams traced as trace_beams traces them without deposition; returns a NamedTuple of one
+n x n_rows matrix per PROFILE_COLUMNS entry (row k: step (k - 1) * cfg.traj_stride, the first the entry
+point; NaN where the ray had stopped) and `state`, `status`, `steps`.  A warm alpha along the ray:
+alpha_warm's inputs are the columns X, Y, N_abs, N_par, Te and 1 ./ dLambda_dN."""
+function ray_profile(p::GPUPlasma, cfg::TraceCfg, beam_off::Vector{Cint}, omega::Vector{Float64},
+                     mode::Vector{Cint}, x0::Matrix{Float64}, N0::Matrix{Float64};
+                     s0::Union{Nothing,Vector{Float64}}=nothing,
+                     plasmas::Union{Nothing,Vector{GPUPlasma}}=nothing,
+                     beam_plasma0::Union{Nothing,Vector{Cint}}=nothing)
+    n = size(x0, 1)
+    n_rows = cfg.traj_stride > 0 ? cfg.n_steps ÷ cfg.traj_stride + 1 : 0
+    hs = plasmas === nothing ? Ptr{Cvoid}[] : _handles(plasmas)
+    prof = zeros(n, length(PROFILE_COLUMNS), n_rows)
+    state, status, steps = zeros(n, 7), zeros(Cint, n), zeros(Cint, n)
+    GC.@preserve plasmas hs beam_plasma0 beam_off omega mode x0 N0 s0 begin
+        check(ccall((:torj_ray_profile, libtorj), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Ref{TraceCfg}, Cint, Ptr{Cint}, Ptr{Float64},
+                     Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Cint}, Ptr{Cint}),
+                    p.h, length(hs), plasmas === nothing ? C_NULL : hs,
+                    beam_plasma0 === nothing ? C_NULL : beam_plasma0, cfg, length(omega), beam_off, omega, mode,
+                    x0, N0, s0 === nothing ? C_NULL : s0, n_rows, prof, state, status, steps))
+    end
+    cols = NamedTuple{PROFILE_COLUMNS}(ntuple(c -> prof[:, c, :], length(PROFILE_COLUMNS)))
+    return merge(cols, (state=state, status=status, steps=steps))
+end
+
 # the device forms: every array but the five host tables is device memory (Ptr{Cvoid}), the call is
 # enqueued on `stream`; torj_trace_check(p, stream) follows the last of them
 function ray_entry_beams_device(p::GPUPlasma, plasmas::Vector{GPUPlasma}, beam_plasma0::Vector{Cint},

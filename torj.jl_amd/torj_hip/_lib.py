@@ -161,6 +161,11 @@ _SIGS = {
     "torj_make_beams": (C.c_int, [C.c_void_p, C.c_int, _hp, C.c_int, C.POINTER(Launcher), C.c_int, C.c_int,
                                   C.POINTER(TraceCfg), C.c_int, _dp, _dp, C.POINTER(BeamResult), _ip,
                                   C.POINTER(BeamsRays)]),
+    # ray profiles: one row of 25 columns per saved point (beam tables and plasmas as above)
+    "torj_ray_profile_device": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.POINTER(TraceCfg), C.c_int, _ip, _dp,
+                                          _ip] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5),
+    "torj_ray_profile": (C.c_int, [C.c_void_p, C.c_int, _hp, _ip, C.POINTER(TraceCfg), C.c_int, _ip, _dp, _ip, _dp,
+                                   _dp, _dp, C.c_int, _dp, _dp, _ip, _ip]),
     "torj_shell_volumes": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "torj_power_deposition_profile": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp,
                                                 _dp, _dp]),

@@ -228,6 +228,58 @@ def trace_beams(plasma, beam_off, omega, mode, x0, N0, *, ds: float = 1e-4, n_st
                        traj.transpose(2, 0, 1).copy() if traj is not None else None)
 
 
+# the columns of a ray profile's rows, in the order of include/torj_hip.h's TORJ_PROF_* enum
+PROFILE_COLUMNS = ("x", "y", "z", "Nx", "Ny", "Nz", "tau", "s", "P", "alpha", "dP_ds", "psi", "ne", "Te",
+                   "Bx", "By", "Bz", "B_abs", "X", "Y", "N_par", "N_abs", "Ns2", "Lambda", "dLambda_dN")
+
+
+@dataclass
+class RayProfile:
+    table: np.ndarray   # (n, n_rows, 25): row k of ray i is step k * traj_stride, NaN where the ray had stopped
+    state: np.ndarray   # (n, 7), status (n,), steps (n,): trace_beams' outputs
+    status: np.ndarray
+    steps: np.ndarray
+    columns = PROFILE_COLUMNS
+
+    def __getitem__(self, name):
+        """column `name` over all rays and rows, (n, n_rows)"""
+        return self.table[:, :, self.columns.index(name)]
+
+
+def ray_profile(plasma, beam_off, omega, mode, x0, N0, *, s0=None, plasmas=None, beam_plasma=None,
+                ds: float = 1e-4, n_steps: int, chunk_steps: int | None = None, traj_stride: int,
+                absorption=True, psi_exit: float = 1.0, P_min: float = 1e-6) -> RayProfile:
+    """N, the plasma parameters and alpha at every saved point of the rays of several
+    beams (torj_ray_profile): the rays are traced as trace_beams traces them without
+    deposition, and row k of ray i holds, at step k * traj_stride (row 0: the entry
+    point), the PROFILE_COLUMNS: x, N, tau, s, P, alpha_approx, dP/ds = P alpha, psi_norm,
+    n_e, T_e, B, |B|, X, Y, N_par, |N|, the cold refractive_index_sq, the dispersion
+    relation Lambda and |dLambda/dN|.  Rows beyond a ray's last step are NaN.  s0
+    (n,): arc lengths at the entry points (None: s counts from there).  plasmas and
+    beam_plasma as in trace_beams.  A warm alpha along the ray is one further call:
+    alpha_warm(omega, r["X"], r["Y"], r["N_abs"], r["N_par"], r["Te"], 1 / r["dLambda_dN"], mode)."""
+    off, om, md = _beam_tables(beam_off, omega, mode)
+    pt = _plasma_tables(plasmas, beam_plasma, len(om))
+    xs, Ns = soa(x0), soa(N0)
+    n = xs.shape[1]
+    if len(off) and off[-1] != n:
+        raise ValueError(f"beam_off[-1] = {off[-1]}, but {n} rays given")
+    if chunk_steps is None:
+        chunk_steps = max(1, n_steps // 100)
+    cfg = TraceCfg(0.0, 0, float(ds), int(n_steps), int(chunk_steps), float(psi_exit), float(P_min),
+                   _absorption_code(absorption), int(traj_stride))
+    sv = f64(s0) if s0 is not None else None
+    n_rows = n_steps // traj_stride + 1 if traj_stride > 0 else 0
+    prof = np.zeros((max(n_rows, 0), len(PROFILE_COLUMNS), n))
+    state = np.zeros((7, n))
+    status = np.zeros(n, dtype=np.int32)
+    steps = np.zeros(n, dtype=np.int32)
+    sel = pt[:3] if pt is not None else (0, None, None)
+    check(lib().torj_ray_profile(plasma.handle, *sel, cfg, len(om), iptr(off), dptr(om), iptr(md), dptr(xs),
+                                 dptr(Ns), dptr(sv), n_rows, dptr(prof), dptr(state), iptr(status), iptr(steps)))
+    return RayProfile(prof.transpose(2, 0, 1).copy(), state.T.copy(), status, steps)
+
+
 def make_ray(plasma, x0, N_vacuum, f: float, mode: int, s_max: float, psi_dP_dV, *,
              ds: float = 1e-4, deposition: str = "reference", integrator: str = "rk4",
              max_steps: int | None = None, absorption="albajar"):
